@@ -2,12 +2,27 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4]
                     [--samples 20000 --features 20000]
+                    [--dump-outputs DIR] [--full]
 
 --config picks a BASELINE.json configuration: cfg4 (default, the headline:
 MultiSURF 20000 x 20000), cfg2 (MultiSURF 5000 x 5000), cfg3 (ReliefF k=10,
 20000 x 2000), cfg5s (SURF* 10000 x 50000), cfg5m (MultiSURF* 10000 x
-50000).  Every line carries the dominant kernel's roofline and, at N=1, a CPU
-baseline from the oracle on a bounded sample of the same workload.
+50000).  Every line carries the dominant kernel's roofline from the HIP events
+of the timed steps.
+
+A plain run does what the headline figure needs and no more: set up, warm
+up, time the K steps, print the line.  --full adds the measurements that take
+runs of their own: at N=1 a CPU baseline from the oracle on a bounded sample
+of the same workload, the 32-bit pass-1 and reference-order step times, the
+timed step's decisions against the committed reference decisions, and (any N)
+the end-to-end fit() timing; --no-cpu-baseline, --no-q32, --no-ref and
+--no-fit drop single ones of them again.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as
+DIR/<name>.npy (rank 0; float32 / float64): `scores` and the per-row near
+hit / miss `counts` of a MultiSURF step, the float64 `sums` of a ReliefF /
+SURF row plan.  The inputs are seeded, so two builds given the same arguments
+can be compared output for output.
 
 For N > 1 launch one process per GPU with torch.distributed.run; the pair
 tiles are sharded round-robin over the ranks and the three small exchange
@@ -24,9 +39,9 @@ rows, pair weights, pass 2 (score accumulation), all-reduces, / n.
 Rank 0 prints ONE JSON line: value = n*p / step time (feature-scores/s, the
 whole job across all ranks), a `roofline` object for the dominant kernel
 (VALU bound; 4 FMA-equivalent FLOPs per pair-feature evaluation)
-measured with HIP events on the stream the kernels run on, and at N=1 a
-`cpu_baseline` from the C oracle (oracle/relief_oracle.c, OpenMP) timed on a
-bounded sample of focal samples of the same data and extrapolated.
+measured with HIP events on the stream the kernels run on, and with --full at
+N=1 a `cpu_baseline` from the C oracle (oracle/relief_oracle.c, OpenMP) timed
+on a bounded sample of focal samples of the same data and extrapolated.
 """
 from __future__ import annotations
 
@@ -139,6 +154,27 @@ def cpu_model():
 
 def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy, float32 or float64.  An
+    output too large for its share of the 64 MB budget is written as a fixed
+    seeded sample of its flattened elements."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype != np.float32:
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize,
+                                                          replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+    log(f"outputs of the last timed step written to {path}: {', '.join(arrays)}")
 
 
 def make_data(n, p, seed, red=100):
@@ -376,8 +412,7 @@ def bench_rows(args, cfg, world, rank, local, on_gpu, dist, sync, barrier, dist_
         if chain:
             from fastselect_amd.parallel import _chain_column_sums
             plan.ref_temp()
-            _chain_column_sums(plan, p, local)
-            return
+            return _chain_column_sums(plan, p, local)
         if world > 1 and on_gpu:
             # the plan runs on its own stream: last step's all-reduce of sums
             # (on torch's stream) must have finished before it writes them
@@ -385,6 +420,7 @@ def bench_rows(args, cfg, world, rank, local, on_gpu, dist, sync, barrier, dist_
         plan.score(sums.data_ptr())
         if world > 1:
             dist.all_reduce(sums, op=dist.ReduceOp.SUM)
+        return sums
 
     for w in range(args.warmup):
         step()
@@ -394,8 +430,9 @@ def bench_rows(args, cfg, world, rank, local, on_gpu, dist, sync, barrier, dist_
     sync()
     t_start = time.perf_counter()
     kms = {0: [], 1: [], 2: []}
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
         if on_gpu:
             for w in kms:
                 kms[w].append(plan.kernel_ms(w))
@@ -406,6 +443,9 @@ def bench_rows(args, cfg, world, rank, local, on_gpu, dist, sync, barrier, dist_
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     ms_per_step = float(t.item()) / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs,
+                     {"sums": last if isinstance(last, np.ndarray) else last.cpu().numpy()})
     roofline = None
     q16 = False
     surf_int = False
@@ -458,7 +498,7 @@ def bench_rows(args, cfg, world, rank, local, on_gpu, dist, sync, barrier, dist_
     plan.close()
     # ReliefF / SURF in reference order beside the default (N = 1): same plan type
     refacc = None
-    if on_gpu and world == 1 and not args.no_ref and args.accumulation == "fast":
+    if args.full and on_gpu and world == 1 and not args.no_ref and args.accumulation == "fast":
         with _lib.accumulation("reference"):
             rplan = _lib.RowsPlan(args.backend, algo, xin, ye, recip, isd, rows=rows,
                                   device=local, stream=stream, **kw)
@@ -506,7 +546,7 @@ def bench_rows(args, cfg, world, rank, local, on_gpu, dist, sync, barrier, dist_
         }
         if refacc is not None:
             out["reference_accumulation"] = refacc
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("timing CPU baseline (oracle) ...")
             out["cpu_baseline"] = cpu_baseline_rows(algo, X, y, cfg.get("k", 0), args.star)
         print(json.dumps(out), flush=True)
@@ -525,15 +565,25 @@ def main():
     ap.add_argument("--features", type=int, default=None)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--star", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: CPU baseline, 32-bit pass-1 "
+                         "and reference-order step times, decisions against the committed "
+                         "reference, end-to-end fit()")
     ap.add_argument("--no-q32", action="store_true",
-                    help="skip the 32-bit pass-1 comparison step time (MultiSURF at N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: skip the 32-bit pass-1 comparison step time (MultiSURF "
+                         "at N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline (N=1)")
     ap.add_argument("--accumulation", default="fast", choices=("fast", "reference"),
                     help="the timed step's accumulation mode (reference: the reference's "
                          "float32 per-sample chains and column sums, bit-identical scores)")
     ap.add_argument("--no-ref", action="store_true",
-                    help="skip the reference-order step time beside the default (N=1)")
-    ap.add_argument("--no-fit", action="store_true", help="skip the end-to-end fit() timing")
+                    help="with --full: skip the reference-order step time beside the default "
+                         "(N=1)")
+    ap.add_argument("--no-fit", action="store_true",
+                    help="with --full: skip the end-to-end fit() timing")
     ap.add_argument("--backend", default="gpu", choices=("gpu", "cpu"),
                     help="cpu: rehearse the multi-rank job on host threads (gloo, tests only)")
     ap.add_argument("--dist-backend", default=None,
@@ -542,6 +592,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     cfg = CONFIGS[args.config]
     args.samples = args.samples or cfg["n"]
     args.features = args.features or cfg["p"]
@@ -625,8 +677,9 @@ def main():
     sync()
     t_start = time.perf_counter()
     dist_ms, score_ms = [], []
+    last = None
     for s in range(args.steps):
-        job.step()
+        last = job.step()
         if on_gpu:
             dist_ms.append(job.kernel_ms(0))
             score_ms.append(job.kernel_ms(1))
@@ -642,6 +695,8 @@ def main():
     elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     n, p = args.samples, args.features
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"scores": last.cpu().numpy(), "counts": step_counts})
 
     roofline = None
     if on_gpu:
@@ -709,7 +764,7 @@ def main():
     # the decision-finer 32-bit pass 1 beside the default step (VERDICT r2
     # next #6): same job, 32-bit operands forced by the q16 test hook
     q32 = None
-    if on_gpu and world == 1 and not args.no_q32 and not ref_mode:
+    if args.full and on_gpu and world == 1 and not args.no_q32 and not ref_mode:
         _lib.set_test_hook("q16", 0)
         try:
             with resident_x(x, args.backend, local):
@@ -731,7 +786,7 @@ def main():
     # the reference-order step beside the default (its
     # cost at cfg2 / cfg4): same job, accumulation='reference'
     refacc = None
-    if on_gpu and world == 1 and not args.no_ref and not ref_mode:
+    if args.full and on_gpu and world == 1 and not args.no_ref and not ref_mode:
         def make_ref():
             with resident_x(x, args.backend, local):
                 return ShardedMultiSURF(x, y, recip, is_disc, use_star=args.star,
@@ -783,7 +838,7 @@ def main():
             # the timed step's near/far decisions against the reference's
             # (VERDICT r4 next #2), when the oracle's decisions are committed
             "decisions_vs_reference": decisions_vs_fixture(step_counts, n, p, args.config)
-            if args.seed == 42 else None,
+            if args.full and args.seed == 42 else None,
         }
         if ref_mode:
             out["arith"] = ("pass 1: integer L1 distances on 32-bit operands, pairs near a "
@@ -795,13 +850,13 @@ def main():
             out["q32_pass1"] = q32
         if refacc is not None:
             out["reference_accumulation"] = refacc
-    if on_gpu and world == 1 and not args.no_fit:
+    if args.full and on_gpu and world == 1 and not args.no_fit:
         log("timing end-to-end fit() ...")
         med, ts = fit_ms(X, y, args.star)
         out["fit_ms"] = med
         out["fit_ms_runs"] = ts
         out["fit_feature_scores_per_s"] = n * p / (med * 1e-3)
-    elif on_gpu and world > 1 and not args.no_fit:
+    elif args.full and on_gpu and world > 1 and not args.no_fit:
         log("timing end-to-end multi-GPU scoring ...")
         med, ts = sharded_fit_ms(X, y, args.star, local, barrier, sync, dist)
         if rank == 0:
@@ -812,7 +867,7 @@ def main():
                                "all-gather of X, column statistics, plan, step, all-reduces; "
                                "max over ranks")
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("timing CPU baseline (oracle) ...")
             out["cpu_baseline"] = cpu_baseline(x, y)
         print(json.dumps(out), flush=True)

@@ -18,6 +18,15 @@ from .SURF import SURF
 from .star import MultiSURFstar, SURFstar
 from .TuRF import TuRF
 
+# The classes shadow their defining submodules here (``fastselect_amd.SURF`` is
+# the class, not the module), so a pickler that resolves ``__module__`` by
+# attribute access cannot find them there and serialises the class by value:
+# dill does, and once a package that uses it (multiprocess, datasets) is
+# imported, so does joblib.dump.  Name the estimators by their public address.
+for _cls in (MultiSURF, ReliefF, SURF, TuRF):
+    _cls.__module__ = __name__
+del _cls
+
 __version__ = "0.1.0"
 __all__ = ["ReliefF", "SURF", "MultiSURF", "SURFstar", "MultiSURFstar", "TuRF"]
 

@@ -51,6 +51,34 @@ def test_bench_gpus2_launches_two_ranks_cpu_rehearsal():
     assert one["roofline"] is None  # no GPU kernels timed in a CPU rehearsal
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """A plain run stops at the headline line; --full adds the measurements
+    with runs of their own; --dump-outputs writes the last timed step's
+    scores and counts, the same from run to run."""
+    a, b = tmp_path / "a", tmp_path / "b"
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    env["OMP_NUM_THREADS"] = "2"
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "cpu",
+            "--samples", "300", "--features", "160", "--steps", "3", "--warmup", "1"]
+    lines = []
+    for extra in (["--dump-outputs", str(a)], ["--dump-outputs", str(b), "--full"]):
+        r = subprocess.run(base + extra, capture_output=True, text=True, env=env, timeout=300,
+                           cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0]))
+    plain, full = lines
+    for d in lines:
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert d["value"] == pytest.approx(300 * 160 / (d["ms_per_step"] * 1e-3))
+    assert "cpu_baseline" not in plain and plain["decisions_vs_reference"] is None
+    assert full["cpu_baseline"]["value"] > 0
+    for name, dtype, shape in (("scores", np.float32, (160,)), ("counts", np.float64, (600,))):
+        x, y = np.load(a / f"{name}.npy"), np.load(b / f"{name}.npy")
+        assert x.dtype == dtype and x.shape == shape and np.isfinite(x).all()
+        np.testing.assert_array_equal(x, y)
+    assert np.abs(np.load(a / "scores.npy")).max() > 0
+
+
 def test_bench_refuses_world_mismatch():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
