@@ -1,0 +1,191 @@
+"""MDR estimator (reference: src/fast_select/MDR.py:148-357).
+
+Multifactor dimensionality reduction: score every k-column combination of a
+0/1/2 genotype matrix by the balanced accuracy of its high/low-risk table,
+pick each cross-validation fold's best model, and keep the model with the
+highest cross-validation consistency.
+
+``fit`` validates as the reference (MDR.py:220-244), draws the reference's
+folds on the host, and makes one call to ``fs_mdr_scan``, which replaces the
+per-fold ``mdr_kernel`` / ``_batch_balanced_accuracy_cpu`` launches and the
+host-built combination list (MDR.py:246-283): all folds come out of one pass
+over bit-plane genotypes, and combinations are addressed by rank.  The per-fold
+lookup tables, test accuracies and the model choice (MDR.py:286-333) stay on
+the host in numpy; they are O(n) per fold.
+
+Arithmetic: cell counts are integers; the risk decision is the integer form
+of the reference's float64 comparison (identical for n < 2^25, and larger n
+is rejected); BA is ``(tp / total_case + tn / total_control) / 2.0`` in IEEE
+float64, rounded to float32.  CPU and GPU backends agree bit for bit.  The
+reference's CPU kernel is ``@njit(fastmath=True)``, which allows LLVM to
+reassociate those three float64 operations; no reference-produced fixture
+pins numba's own bits, so parity with them is unpinned (as for the Relief
+kernels).
+"""
+from __future__ import annotations
+
+from collections import Counter
+
+import numpy as np
+from sklearn.base import BaseEstimator, ClassifierMixin
+from sklearn.model_selection import StratifiedKFold
+from sklearn.utils.multiclass import unique_labels
+from sklearn.utils.validation import check_array, check_is_fitted, check_X_y
+
+from . import _base, _lib
+
+MAX_K_FOR_KERNEL = 6
+
+
+def cell_index(X, interaction):
+    """``cell = cell * 3 + genotype`` over the interaction's columns, first
+    column most significant (MDR.py:41-45)."""
+    cell = np.zeros(X.shape[0], dtype=np.int64)
+    for j in interaction:
+        cell = cell * 3 + X[:, j]
+    return cell
+
+
+def lookup_table(X, y, interaction):
+    """The 3^k high-risk table of ``_create_lookup_table`` (MDR.py:176-195):
+    ``case / (control + 1e-9) > total_case / total_control`` in float64 (an
+    empty cell is low risk here, unlike in the scan)."""
+    n_cells = 3 ** len(interaction)
+    cell = cell_index(X, interaction)
+    case = np.bincount(cell[y == 1], minlength=n_cells).astype(np.int32)
+    control = np.bincount(cell[y != 1], minlength=n_cells).astype(np.int32)
+    total_cases = case.sum()
+    total_controls = control.sum()
+    threshold = np.inf if total_controls == 0 else total_cases / total_controls
+    ratios = case / (control + 1e-9)
+    return (ratios > threshold).astype(np.uint8)
+
+
+class MDR(ClassifierMixin, BaseEstimator):
+    """Multifactor dimensionality reduction on the MI355X or the CPU.
+
+    All features must be SNP genotypes coded 0, 1, 2; ``y`` must hold two
+    labels, and a sample is a case iff its label equals 1.
+
+    Parameters
+    ----------
+    k : int, default=2
+        Interaction order to search (at most 6).
+    cv : int, default=10
+        Stratified folds for model selection (shuffled, random_state=42).
+    backend : {'auto', 'cpu', 'gpu'}, default='auto'
+        Execution backend, case-insensitive.  'gpu' without a visible HIP
+        device raises; it never falls back.
+    verbose : bool, default=False
+        Print progress information during training.
+    n_jobs : int, default=-1
+        CPU threads for backend='cpu' (-1 = all).  Not a reference parameter.
+    device : int, default=0
+        GPU ordinal for the GPU backend.  Not a reference parameter.
+
+    Attributes
+    ----------
+    best_interaction_ : tuple of int
+    best_cvc_ : int
+    best_mean_testing_ba_ : float
+    best_model_lookup_table_ : ndarray of uint8, shape (3**k,)
+    classes_, n_features_in_, effective_backend_
+    """
+
+    def __init__(self, k: int = 2, cv: int = 10, backend: str = "auto", verbose: bool = False,
+                 n_jobs: int = -1, device: int = 0):
+        self.k = k
+        self.cv = cv
+        self.backend = backend
+        self.verbose = verbose
+        self.n_jobs = n_jobs
+        self.device = device
+
+    def fit(self, X, y):
+        """Find the best k-way interaction by cross-validated MDR."""
+        X, y = check_X_y(X, y, dtype=np.uint8)
+        self.classes_ = unique_labels(y)
+        if len(self.classes_) != 2:
+            raise ValueError("MDR only supports binary classification.")
+        if np.max(X) > 2 or np.min(X) < 0:
+            raise ValueError("Genotypes must be coded 0/1/2.")
+        if self.k > MAX_K_FOR_KERNEL:
+            raise ValueError(f"k={self.k} exceeds MAX_K_FOR_KERNEL={MAX_K_FOR_KERNEL}.")
+        n_samples, n_features = X.shape
+        if self.k > n_features:
+            raise ValueError(f"k must be ≤ n_features. Got k={self.k}, n_features={n_features}")
+        backend = self.backend.lower() if isinstance(self.backend, str) else self.backend
+        if backend not in ("auto", "cpu", "gpu"):
+            raise ValueError("backend must be 'auto', 'CPU', or 'GPU'.")
+        self.effective_backend_ = _base.effective_backend(backend)
+        self.n_features_in_ = n_features
+        k = int(self.k)
+
+        X = np.ascontiguousarray(X)
+        skf = StratifiedKFold(n_splits=self.cv, shuffle=True, random_state=42)
+        splits = list(skf.split(X, y))
+        fold = np.empty(n_samples, dtype=np.int32)
+        for i, (_, test_idx) in enumerate(splits):
+            fold[test_idx] = i
+        if self.verbose:
+            print(f"CV with backend={self.effective_backend_.upper()}: {k}-way search over "
+                  f"{_lib.mdr_combinations(n_features, k)} combos")
+        _, best_rank = _lib.mdr_scan(self.effective_backend_, X, y == 1, k, fold, len(splits),
+                                     device=self.device, n_jobs=self.n_jobs)
+
+        fold_best_models = []
+        fold_test_bas = []
+        for fold_i, (train_idx, test_idx) in enumerate(splits):
+            best_combo = _lib.mdr_unrank(n_features, k, int(best_rank[fold_i]))
+            fold_best_models.append(best_combo)
+            lookup = lookup_table(X[train_idx], y[train_idx], best_combo)
+            y_test = y[test_idx]
+            y_pred_test = lookup[cell_index(X[test_idx], best_combo)]
+            tp = np.sum((y_test == 1) & (y_pred_test == 1))
+            tn = np.sum((y_test == 0) & (y_pred_test == 0))
+            n_pos = np.sum(y_test == 1)
+            n_neg = np.sum(y_test == 0)
+            sens = tp / n_pos if n_pos else 0
+            spec = tn / n_neg if n_neg else 0
+            test_ba = (sens + spec) / 2.0
+            fold_test_bas.append(test_ba)
+            if self.verbose:
+                print(f"  Fold {fold_i + 1}/{self.cv}: best {best_combo}, Test BA = {test_ba:.4f}")
+
+        counts = Counter(fold_best_models)
+        max_cvc = counts.most_common(1)[0][1]
+        best_model, best_avg_ba = None, -1.0
+        for model in (m for m, c in counts.items() if c == max_cvc):
+            avg_ba = float(np.mean([fold_test_bas[i] for i, m in enumerate(fold_best_models)
+                                    if m == model]))
+            if avg_ba > best_avg_ba:
+                best_avg_ba, best_model = avg_ba, model
+
+        self.best_interaction_ = best_model
+        self.best_cvc_ = max_cvc
+        self.best_mean_testing_ba_ = best_avg_ba
+        if self.verbose:
+            print("\nFit Complete")
+            print(f"Best interaction: {self.best_interaction_}")
+            print(f"CVC: {self.best_cvc_}/{self.cv}")
+            print(f"Mean testing BA: {self.best_mean_testing_ba_:.4f}")
+        self.best_model_lookup_table_ = lookup_table(X, y, self.best_interaction_)
+        return self
+
+    def predict(self, X):
+        """1 for samples in a high-risk cell of the best interaction, else 0."""
+        check_is_fitted(self)
+        X = check_array(X, dtype=np.uint8)
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, but MDR is expecting "
+                             f"{self.n_features_in_} features as input.")
+        if np.max(X[:, list(self.best_interaction_)], initial=0) > 2:
+            raise ValueError("Genotypes must be coded 0/1/2.")
+        return self.best_model_lookup_table_[cell_index(X, self.best_interaction_)]
+
+    def transform(self, X):
+        return self.predict(X).reshape(-1, 1)
+
+    def predict_proba(self, X):
+        """Not implemented: MDR is a hard classifier (as in the reference)."""
+        raise NotImplementedError("predict_proba is not supported in this MDR implementation.")

@@ -49,6 +49,7 @@ EXPORTED = (
     "fs_plan_destroy", "fs_multisurf_score_devices", "fs_relieff_score_devices",
     "fs_surf_score_devices", "fs_set_accumulation", "fs_get_accumulation", "fs_test_hook",
     "fs_multisurf_score_ex", "fs_relieff_score_ex", "fs_surf_score_ex",
+    "fs_mdr_scan", "fs_mdr_combinations", "fs_mdr_unrank",
 )
 
 
@@ -159,6 +160,13 @@ def _load() -> ctypes.CDLL:
     lib.fs_get_accumulation.restype = _int
     lib.fs_test_hook.argtypes = [ctypes.c_char_p, _i64]
     lib.fs_test_hook.restype = _int
+    lib.fs_mdr_scan.argtypes = [_int, _int, _u8p, _i64, _i64, _u8p, _int, _i32p, _int, _int, _f32p,
+                                _i64p, _f32p]
+    lib.fs_mdr_scan.restype = _int
+    lib.fs_mdr_combinations.argtypes = [_i64, _int, _i64p]
+    lib.fs_mdr_combinations.restype = _int
+    lib.fs_mdr_unrank.argtypes = [_i64, _int, _i64, _i32p]
+    lib.fs_mdr_unrank.restype = _int
     for name in ("fs_column_stats", "fs_multisurf_score", "fs_multisurf_score_rows",
                  "fs_plan_set_rows", "fs_relieff_score", "fs_surf_score",
                  "fs_relieff_score_rows", "fs_surf_score_rows", "fs_plan_create",
@@ -702,3 +710,56 @@ class RowsPlan(Plan):
         """Reference order: the score up to the float32 temp rows, whose column
         sums ``ref_sums`` continues (``fs_plan_ref_temp``; ReliefF, SURF)."""
         check(_lib.fs_plan_ref_temp(self._h))
+
+
+def mdr_combinations(p: int, k: int) -> int:
+    """C(p, k), the number of combinations ``mdr_scan`` scores
+    (``fs_mdr_combinations``); ValueError above 2^62."""
+    c = _i64(0)
+    check(_lib.fs_mdr_combinations(int(p), int(k), ctypes.byref(c)))
+    return int(c.value)
+
+
+def mdr_unrank(p: int, k: int, rank: int):
+    """The combination at ``rank`` in ``itertools.combinations(range(p), k)``
+    order as a tuple of ints (``fs_mdr_unrank``): the reference's
+    ``all_combos[rank]`` (MDR.py:283) without the list."""
+    f = np.empty(int(k) if 1 <= int(k) <= 6 else 6, dtype=np.int32)
+    check(_lib.fs_mdr_unrank(int(p), int(k), int(rank), _p(f, _i32p)))
+    return tuple(int(v) for v in f[:k])
+
+
+def mdr_scan(backend, x, is_case, k, fold=None, n_folds=0, device=0, n_jobs=-1, want_ba=False):
+    """Balanced accuracy of every k-combination of the genotype columns of
+    ``x`` (uint8, values 0/1/2) for all folds in one pass (``fs_mdr_scan``;
+    replaces ``mdr_kernel`` / ``_batch_balanced_accuracy_cpu``, MDR.py:20-129).
+
+    ``fold[i]`` is the fold whose test set holds sample i; ``fold=None``
+    trains one scan on all samples.  Returns (best_ba float32[F], best_rank
+    int64[F]) with F = max(n_folds, 1), plus the F x C(p,k) float32 array of
+    every BA when ``want_ba`` (small jobs only)."""
+    x = np.ascontiguousarray(x, dtype=np.uint8)
+    if x.ndim != 2:
+        raise ValueError("x must be a 2-D array")
+    n, p = x.shape
+    case = np.ascontiguousarray(is_case, dtype=np.uint8)
+    if case.shape != (n,):
+        raise ValueError("is_case must have one entry per row of x")
+    fv = None
+    if fold is not None:
+        fv = np.ascontiguousarray(fold, dtype=np.int32)
+        if fv.shape != (n,):
+            raise ValueError("fold must have one entry per row of x")
+    else:
+        n_folds = 0
+    nf = max(int(n_folds), 1)
+    best_ba = np.zeros(nf, dtype=np.float32)
+    best_rank = np.zeros(nf, dtype=np.int64)
+    ba = None
+    if want_ba:
+        ba = np.zeros((nf, mdr_combinations(p, k)), dtype=np.float32)
+    check(_lib.fs_mdr_scan(_backend_code(backend), int(device), _p(x, _u8p), n, p, _p(case, _u8p),
+                           int(k), None if fv is None else _p(fv, _i32p), int(n_folds),
+                           int(n_jobs), _p(best_ba, _f32p), _p(best_rank, _i64p),
+                           None if ba is None else _p(ba, _f32p)))
+    return (best_ba, best_rank, ba) if want_ba else (best_ba, best_rank)

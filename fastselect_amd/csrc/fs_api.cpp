@@ -8,6 +8,7 @@
 
 #include "../../include/fastselect_amd.h"
 #include "fs_internal.h"
+#include "fs_mdr.h"
 
 #include <chrono>
 #include <cstdio>
@@ -1004,6 +1005,44 @@ int fs_plan_destroy(fs_plan* pl) {
   if (!pl) return FS_OK;
   if (pl->g) gpu::plan_destroy(pl->g);
   delete pl;
+  return FS_OK;
+}
+
+int fs_mdr_scan(int backend, int device, const uint8_t* x, int64_t n, int64_t p,
+                const uint8_t* is_case, int k, const int32_t* fold, int n_folds, int n_jobs,
+                float* best_ba, int64_t* best_rank, float* ba_out) {
+  int rc = check_backend(backend, device);
+  if (rc != FS_OK) return rc;
+  int64_t count = 0;
+  if ((rc = mdr_check(x, n, p, is_case, k, fold, n_folds, best_ba, best_rank, &count)) != FS_OK)
+    return rc;
+  if (backend == FS_BACKEND_GPU)
+    return gpu::mdr_scan(device, x, n, p, is_case, k, fold, n_folds, count, best_ba, best_rank,
+                         ba_out);
+  return cpu::mdr_scan(x, n, p, is_case, k, fold, n_folds, n_jobs, count, best_ba, best_rank,
+                       ba_out);
+}
+
+int fs_mdr_combinations(int64_t p, int k, int64_t* count) {
+  if (!count || k < 1 || k > kMdrMaxK || p < k) {
+    set_error("fs_mdr_combinations: need count, k in 1..6 and p >= k");
+    return FS_EINVAL;
+  }
+  if (!mdr_count(p, k, count)) {
+    set_error("fs_mdr_combinations: C(p,k) exceeds 2^62");
+    return FS_EINVAL;
+  }
+  return FS_OK;
+}
+
+int fs_mdr_unrank(int64_t p, int k, int64_t rank, int32_t* features) {
+  int64_t count = 0;
+  if (!features || k < 1 || k > kMdrMaxK || p < k || !mdr_count(p, k, &count) || rank < 0 ||
+      rank >= count) {
+    set_error("fs_mdr_unrank: need features, k in 1..6, p >= k and rank in [0, C(p,k))");
+    return FS_EINVAL;
+  }
+  mdr_unrank(p, k, rank, features);
   return FS_OK;
 }
 

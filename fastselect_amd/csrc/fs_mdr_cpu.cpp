@@ -1,0 +1,256 @@
+// fs_mdr_cpu.cpp -- MDR's sample layout and argument checks (both backends)
+// and the CPU backend of fs_mdr_scan: the bit-plane / popcount scheme of
+// fs_mdr.h on 64-bit words, the rank range split over host threads.  It
+// replaces _batch_balanced_accuracy_cpu (MDR.py:82-129) for all folds at once.
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <thread>
+
+#include "../../include/fastselect_amd.h"
+#include "fs_mdr.h"
+
+namespace fs {
+
+int mdr_layout(int64_t n, const uint8_t* is_case, const int32_t* fold, int n_folds, int wordbits,
+               MdrLayout& L) {
+  const int F = fold ? n_folds : 1;
+  L.F = F;
+  L.sub = fold ? 1 : 0;
+  std::vector<int64_t> size(2 * (size_t)F, 0);
+  for (int64_t i = 0; i < n; i++) {
+    const int f = fold ? fold[i] : 0;
+    if (f < 0 || f >= F) {
+      set_error("fs_mdr_scan: fold id outside [0, n_folds)");
+      return FS_EINVAL;
+    }
+    size[(size_t)(is_case[i] ? 0 : 1) * F + f]++;
+  }
+  L.seg_off.assign(2 * (size_t)F + 1, 0);
+  int64_t w = 0;
+  for (int s = 0; s < 2 * F; s++) {
+    L.seg_off[s] = (int32_t)w;
+    w += (size[s] + wordbits - 1) / wordbits;
+  }
+  L.seg_off[2 * F] = (int32_t)w;
+  L.words = w;
+  L.perm.assign((size_t)w * wordbits, -1);
+  std::vector<int64_t> fill(2 * (size_t)F);
+  for (int s = 0; s < 2 * F; s++) fill[s] = (int64_t)L.seg_off[s] * wordbits;
+  for (int64_t i = 0; i < n; i++) {
+    const size_t s = (size_t)(is_case[i] ? 0 : 1) * F + (fold ? fold[i] : 0);
+    L.perm[fill[s]++] = (int32_t)i;
+  }
+  int64_t cases = 0;
+  for (int f = 0; f < F; f++) cases += size[f];
+  L.tc.resize(F);
+  L.tn.resize(F);
+  for (int f = 0; f < F; f++) {
+    L.tc[f] = cases - (L.sub ? size[f] : 0);
+    L.tn[f] = (n - cases) - (L.sub ? size[(size_t)F + f] : 0);
+  }
+  return FS_OK;
+}
+
+int mdr_check(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int k,
+              const int32_t* fold, int n_folds, const float* best_ba, const int64_t* best_rank,
+              int64_t* count) {
+  if (!x || !is_case || !best_ba || !best_rank) {
+    set_error("fs_mdr_scan: x, is_case, best_ba and best_rank must not be NULL");
+    return FS_EINVAL;
+  }
+  if (k < 1 || k > kMdrMaxK) {
+    set_error("fs_mdr_scan: k must be in 1..6");
+    return FS_EINVAL;
+  }
+  if (n < 1 || n >= kMdrMaxN) {
+    set_error("fs_mdr_scan: n must be in [1, 2^25)");
+    return FS_EINVAL;
+  }
+  if (p < k) {
+    set_error("fs_mdr_scan: k must be <= the number of columns");
+    return FS_EINVAL;
+  }
+  if ((fold == nullptr) != (n_folds == 0) || n_folds < 0 || n_folds > n) {
+    set_error("fs_mdr_scan: fold and n_folds go together (NULL and 0, or ids and 1..n)");
+    return FS_EINVAL;
+  }
+  if (!mdr_count(p, k, count)) {
+    set_error("fs_mdr_scan: C(p,k) exceeds 2^62");
+    return FS_EINVAL;
+  }
+  return FS_OK;
+}
+
+namespace cpu {
+
+namespace {
+
+// planes[(j * 3 + g) * W + w]: bit b of word w is set iff the sample at
+// position w * 64 + b of the layout has genotype g in column j.
+int pack_planes(const uint8_t* x, int64_t p, const MdrLayout& L, int n_jobs,
+                std::vector<uint64_t>& planes) {
+  const int64_t W = L.words;
+  planes.assign((size_t)p * 3 * W, 0);
+  std::atomic<int> bad{0};
+  const int64_t kBlock = 64;  // columns per task
+  const int64_t tasks = (p + kBlock - 1) / kBlock;
+  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(hardware_threads(n_jobs), tasks));
+  std::atomic<int64_t> next{0};
+  auto work = [&]() {
+    for (int64_t t = next++; t < tasks; t = next++) {
+      const int64_t j0 = t * kBlock, j1 = std::min(p, j0 + kBlock);
+      bool b = false;
+      for (int64_t pos = 0; pos < W * 64; pos++) {
+        const int32_t i = L.perm[pos];
+        if (i < 0) continue;
+        const uint8_t* row = x + (size_t)i * p;
+        const uint64_t bit = 1ull << (pos & 63);
+        for (int64_t j = j0; j < j1; j++) {
+          const uint8_t g = row[j];
+          if (g > 2) { b = true; continue; }
+          planes[((size_t)j * 3 + g) * W + (pos >> 6)] |= bit;
+        }
+      }
+      if (b) bad.store(1, std::memory_order_relaxed);
+    }
+  };
+  std::vector<std::thread> th;
+  for (int w = 1; w < nt; w++) th.emplace_back(work);
+  work();
+  for (auto& t : th) t.join();
+  if (bad.load()) {
+    set_error("fs_mdr_scan: genotypes must be coded 0/1/2");
+    return FS_EINVAL;
+  }
+  return FS_OK;
+}
+
+struct Best {
+  uint32_t bits = 0;
+  int64_t rank = kMdrNoRank;
+};
+
+// The scan is popcounts: on x86-64 the build's baseline has no popcnt
+// instruction, so the loop is compiled twice and the call picks the hardware
+// one where the CPU has it (every x86-64 CPU of the last decade).
+#if defined(__x86_64__) && defined(__GNUC__)
+#define FS_MDR_POPCNT __attribute__((target("popcnt")))
+inline bool have_popcnt() { return __builtin_cpu_supports("popcnt"); }
+#else
+#define FS_MDR_POPCNT
+inline bool have_popcnt() { return false; }
+#endif
+
+// One combination: tp / tn of every fold.  cnt is 3 x 2F scratch.
+template <bool HW>
+__attribute__((always_inline)) inline void scan_one(const uint64_t* planes, int64_t W, const MdrLayout& L, int k,
+                     const int32_t* f, uint32_t* cnt, uint64_t* tp, uint64_t* tn) {
+  const int F = L.F, S = 2 * F;
+  int cells = 1;
+  for (int t = 1; t < k; t++) cells *= 3;
+  for (int i = 0; i < F; i++) tp[i] = tn[i] = 0;
+  const uint64_t* last = planes + (size_t)f[k - 1] * 3 * W;
+  const uint64_t* pre[kMdrMaxK];
+  for (int cell = 0; cell < cells; cell++) {
+    for (int t = k - 2, c = cell; t >= 0; t--, c /= 3)
+      pre[t] = planes + ((size_t)f[t] * 3 + c % 3) * W;
+    uint32_t tot[3][2] = {{0, 0}, {0, 0}, {0, 0}};
+    for (int s = 0; s < S; s++) {
+      uint32_t a0 = 0, a1 = 0, a2 = 0;
+      for (int64_t w = L.seg_off[s]; w < L.seg_off[s + 1]; w++) {
+        uint64_t m = ~0ull;
+        for (int t = 0; t < k - 1; t++) m &= pre[t][w];
+        a0 += (uint32_t)__builtin_popcountll(m & last[w]);
+        a1 += (uint32_t)__builtin_popcountll(m & last[W + w]);
+        a2 += (uint32_t)__builtin_popcountll(m & last[2 * W + w]);
+      }
+      cnt[s] = a0, cnt[S + s] = a1, cnt[2 * S + s] = a2;
+      const int c = s >= F;
+      tot[0][c] += a0, tot[1][c] += a1, tot[2][c] += a2;
+    }
+    for (int g = 0; g < 3; g++)
+      for (int i = 0; i < F; i++) {
+        const uint32_t cs = tot[g][0] - (L.sub ? cnt[g * S + i] : 0);
+        const uint32_t ct = tot[g][1] - (L.sub ? cnt[g * S + F + i] : 0);
+        if (mdr_high_risk(cs, ct, (uint64_t)L.tc[i], (uint64_t)L.tn[i])) tp[i] += cs;
+        else tn[i] += ct;
+      }
+  }
+}
+
+using ScanFn = void (*)(const uint64_t*, int64_t, const MdrLayout&, int, const int32_t*, uint32_t*,
+                        uint64_t*, uint64_t*);
+void scan_one_sw(const uint64_t* planes, int64_t W, const MdrLayout& L, int k, const int32_t* f,
+                 uint32_t* cnt, uint64_t* tp, uint64_t* tn) {
+  scan_one<false>(planes, W, L, k, f, cnt, tp, tn);
+}
+FS_MDR_POPCNT void scan_one_hw(const uint64_t* planes, int64_t W, const MdrLayout& L, int k,
+                               const int32_t* f, uint32_t* cnt, uint64_t* tp, uint64_t* tn) {
+  scan_one<true>(planes, W, L, k, f, cnt, tp, tn);
+}
+
+}  // namespace
+
+int mdr_scan(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int k,
+             const int32_t* fold, int n_folds, int n_jobs, int64_t count, float* best_ba,
+             int64_t* best_rank, float* ba_out) {
+  MdrLayout L;
+  if (int rc = mdr_layout(n, is_case, fold, n_folds, 64, L)) return rc;
+  std::vector<uint64_t> planes;
+  try {
+    if (int rc = pack_planes(x, p, L, n_jobs, planes)) return rc;
+  } catch (const std::bad_alloc&) {
+    set_error("fs_mdr_scan: out of host memory for the genotype planes");
+    return FS_EOOM;
+  }
+  const int F = L.F;
+  const int64_t W = L.words;
+  const ScanFn scan = have_popcnt() ? scan_one_hw : scan_one_sw;
+  // contiguous rank chunks, several per thread; each keeps its own best, and
+  // the chunks merge in rank order (the result does not depend on threads)
+  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(hardware_threads(n_jobs), count));
+  const int64_t chunks = std::min<int64_t>(count, (int64_t)nt * 8);
+  std::vector<Best> best((size_t)chunks * F);
+  std::atomic<int64_t> next{0};
+  auto work = [&]() {
+    std::vector<uint32_t> cnt(6 * (size_t)F);
+    std::vector<uint64_t> tp(F), tn(F);
+    int32_t f[kMdrMaxK];
+    for (int64_t c = next++; c < chunks; c = next++) {
+      const int64_t r0 = (int64_t)((__int128)count * c / chunks);
+      const int64_t r1 = (int64_t)((__int128)count * (c + 1) / chunks);
+      if (r0 >= r1) continue;
+      mdr_unrank(p, k, r0, f);
+      Best* b = &best[(size_t)c * F];
+      for (int64_t r = r0; r < r1; r++) {
+        if (r > r0) mdr_next(p, k, f);
+        scan(planes.data(), W, L, k, f, cnt.data(), tp.data(), tn.data());
+        for (int i = 0; i < F; i++) {
+          const float ba = mdr_ba(tp[i], tn[i], (uint64_t)L.tc[i], (uint64_t)L.tn[i]);
+          if (ba_out) ba_out[(size_t)i * count + r] = ba;
+          uint32_t bits;
+          std::memcpy(&bits, &ba, 4);
+          if (mdr_better(bits, r, b[i].bits, b[i].rank)) b[i].bits = bits, b[i].rank = r;
+        }
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (int w = 1; w < nt; w++) th.emplace_back(work);
+  work();
+  for (auto& t : th) t.join();
+  for (int i = 0; i < F; i++) {
+    Best m;
+    for (int64_t c = 0; c < chunks; c++) {
+      const Best& b = best[(size_t)c * F + i];
+      if (mdr_better(b.bits, b.rank, m.bits, m.rank)) m = b;
+    }
+    std::memcpy(&best_ba[i], &m.bits, 4);
+    best_rank[i] = m.rank;
+  }
+  return FS_OK;
+}
+
+}  // namespace cpu
+}  // namespace fs

@@ -510,6 +510,44 @@ FS_API int fs_plan_weighted_pairs(const fs_plan* plan, int64_t* pairs);
 FS_API double fs_plan_kernel_ms(const fs_plan* plan, int which);
 FS_API int fs_plan_destroy(fs_plan* plan);
 
+/* ---- MDR: exhaustive k-way SNP interaction search ----------------------- */
+
+/*
+ * Balanced accuracy of every k-combination of the p genotype columns, for all
+ * cross-validation folds in one pass.  Replaces mdr_kernel (MDR.py:20-79) and
+ * _batch_balanced_accuracy_cpu (MDR.py:82-129), which the reference's fit
+ * calls once per fold on a host-built list of combinations (MDR.py:246-283).
+ *   x          [n][p] row-major genotypes in {0,1,2} (the uint8 X of MDR.py:220)
+ *   is_case    [n] nonzero marks a case (y == 1, MDR.py:47, 102)
+ *   fold       [n] in [0, n_folds): the fold whose TEST set holds sample i;
+ *              fold f trains on every sample with fold[i] != f.  fold == NULL
+ *              and n_folds == 0: one scan that trains on all samples (outputs
+ *              have length 1)
+ *   n_jobs     CPU threads (-1 = all); ignored by the GPU backend
+ *   best_ba    [max(n_folds,1)] the largest float32 BA of each fold
+ *   best_rank  [max(n_folds,1)] the smallest combination rank
+ *              (itertools.combinations order) that attains it, i.e.
+ *              np.argmax of the fold's BAs (MDR.py:282)
+ *   ba_out     NULL, or [max(n_folds,1)][C(p,k)] float32, fold-major (sized by
+ *              the caller; for tests and small jobs)
+ * Cell counts are popcounts of ANDed genotype bit-planes; a cell is high risk
+ * iff control == 0 or case * total_control > control * total_case, which
+ * equals the reference's float64 comparison for n < 2^25; BA = (tp /
+ * total_case + tn / total_control) / 2.0 in IEEE float64, rounded to float32.
+ * Both backends give the same bits.  FS_EINVAL: k outside 1..6, k > p, n < 1
+ * or n >= 2^25, a genotype above 2, a fold id out of range, C(p,k) > 2^62,
+ * NULL pointers.
+ */
+FS_API int fs_mdr_scan(int backend, int device, const uint8_t* x, int64_t n, int64_t p,
+                       const uint8_t* is_case, int k, const int32_t* fold, int n_folds,
+                       int n_jobs, float* best_ba, int64_t* best_rank, float* ba_out);
+/* C(p,k), the length of np.array(list(combinations(range(p), k))) that the
+ * reference builds on the host (MDR.py:247-251); FS_EINVAL if above 2^62. */
+FS_API int fs_mdr_combinations(int64_t p, int k, int64_t* count);
+/* rank -> the k ascending column indices of that combination, i.e.
+ * all_combos[rank] of the reference (MDR.py:283), without the list. */
+FS_API int fs_mdr_unrank(int64_t p, int k, int64_t rank, int32_t* features);
+
 #ifdef __cplusplus
 }
 #endif
