@@ -8,13 +8,16 @@ scikit-learn surface.  Scoring runs in hand-written HIP kernels for gfx950
 (``fastselect_amd/csrc``) behind the C ABI in ``include/fastselect_amd.h``;
 ``fastselect_amd.parallel`` shards MultiSURF over one process per GPU.
 ``MDR`` is the reference's exhaustive k-way SNP interaction search, the usual
-second stage after a Relief filter.
+second stage after a Relief filter; ``mRMR`` (with the
+``fastselect_amd.mutual_information`` functions it is built on) drops
+redundant features in between.
 
 Importing the package loads the native library; it fails loudly if the
 library has not been built.
 """
-from . import _lib
+from . import _lib, mutual_information
 from .MDR import MDR
+from .mRMR import mRMR
 from .MultiSURF import MultiSURF
 from .ReliefF import ReliefF
 from .SURF import SURF
@@ -26,12 +29,12 @@ from .TuRF import TuRF
 # attribute access cannot find them there and serialises the class by value:
 # dill does, and once a package that uses it (multiprocess, datasets) is
 # imported, so does joblib.dump.  Name the estimators by their public address.
-for _cls in (MultiSURF, ReliefF, SURF, TuRF, MDR):
+for _cls in (MultiSURF, ReliefF, SURF, TuRF, MDR, mRMR):
     _cls.__module__ = __name__
 del _cls
 
 __version__ = "0.1.0"
-__all__ = ["ReliefF", "SURF", "MultiSURF", "SURFstar", "MultiSURFstar", "TuRF", "MDR"]
+__all__ = ["ReliefF", "SURF", "MultiSURF", "SURFstar", "MultiSURFstar", "TuRF", "MDR", "mRMR"]
 
 
 def gpu_available() -> bool:

@@ -50,6 +50,7 @@ EXPORTED = (
     "fs_surf_score_devices", "fs_set_accumulation", "fs_get_accumulation", "fs_test_hook",
     "fs_multisurf_score_ex", "fs_relieff_score_ex", "fs_surf_score_ex",
     "fs_mdr_scan", "fs_mdr_combinations", "fs_mdr_unrank",
+    "fs_mi_matrices", "fs_mi_last_timing",
 )
 
 
@@ -167,6 +168,11 @@ def _load() -> ctypes.CDLL:
     lib.fs_mdr_combinations.restype = _int
     lib.fs_mdr_unrank.argtypes = [_i64, _int, _i64, _i32p]
     lib.fs_mdr_unrank.restype = _int
+    lib.fs_mi_matrices.argtypes = [_int, _int, _u8p, _u8p, _i64, _i64, _int, _int, _int, _f64p,
+                                   _f64p, _i32p]
+    lib.fs_mi_matrices.restype = _int
+    lib.fs_mi_last_timing.argtypes = [_f64p]
+    lib.fs_mi_last_timing.restype = _int
     for name in ("fs_column_stats", "fs_multisurf_score", "fs_multisurf_score_rows",
                  "fs_plan_set_rows", "fs_relieff_score", "fs_surf_score",
                  "fs_relieff_score_rows", "fs_surf_score_rows", "fs_plan_create",
@@ -763,3 +769,44 @@ def mdr_scan(backend, x, is_case, k, fold=None, n_folds=0, device=0, n_jobs=-1, 
                            int(n_jobs), _p(best_ba, _f32p), _p(best_rank, _i64p),
                            None if ba is None else _p(ba, _f32p)))
     return (best_ba, best_rank, ba) if want_ba else (best_ba, best_rank)
+
+
+MI_UNITS = {"bit": 0, "nat": 1}
+
+
+def mi_matrices(backend, codes, ycodes, n_states, unit="bit", n_jobs=-1, device=0,
+                want_counts=False):
+    """Relevance I(X_f; y) and the p x p matrix of pairwise mutual information
+    of state codes (``fs_mi_matrices``; replaces ``_batch_mi_cpu`` and
+    ``_mi_pair_gpu_kernel``, mutual_information.py:49-115).
+
+    ``codes`` (n x p) and ``ycodes`` (n) hold values in ``0..n_states-1``
+    (uint8).  Returns (relevance float64[p], redundancy float64[p, p]), plus
+    the int32 [p, p, n_states, n_states] contingency tables of the pairs
+    i < j when ``want_counts`` (small jobs only)."""
+    x = np.ascontiguousarray(codes, dtype=np.uint8)
+    if x.ndim != 2:
+        raise ValueError("codes must be a 2-D array")
+    n, p = x.shape
+    yv = np.ascontiguousarray(ycodes, dtype=np.uint8)
+    if yv.shape != (n,):
+        raise ValueError("ycodes must have one entry per row of codes")
+    if unit not in MI_UNITS:
+        raise ValueError("unit must be 'bit' or 'nat'")
+    rel = np.zeros(p, dtype=np.float64)
+    red = np.zeros((p, p), dtype=np.float64)
+    cnt = None
+    if want_counts:
+        cnt = np.zeros((p, p, int(n_states), int(n_states)), dtype=np.int32)
+    check(_lib.fs_mi_matrices(_backend_code(backend), int(device), _p(x, _u8p), _p(yv, _u8p), n, p,
+                              int(n_states), MI_UNITS[unit], int(n_jobs), _p(rel, _f64p),
+                              _p(red, _f64p), None if cnt is None else _p(cnt, _i32p)))
+    return (rel, red, cnt) if want_counts else (rel, red)
+
+
+def mi_last_timing():
+    """(upload, pack, scan, download) milliseconds of this thread's last GPU
+    ``mi_matrices`` (``fs_mi_last_timing``; -1 where unavailable)."""
+    v = np.full(4, -1.0)
+    check(_lib.fs_mi_last_timing(_p(v, _f64p)))
+    return tuple(float(t) for t in v)

@@ -9,6 +9,7 @@
 #include "../../include/fastselect_amd.h"
 #include "fs_internal.h"
 #include "fs_mdr.h"
+#include "fs_mi.h"
 
 #include <chrono>
 #include <cstdio>
@@ -152,6 +153,7 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "colsort_star") h.colsort_star = value;
   else if (k == "colsort_bins12") h.colsort_bins12 = value;
   else if (k == "colsort_global") h.colsort_global = value;
+  else if (k == "mi_tiles") h.mi_tiles = value;
   else {
     set_error("fs_test_hook: unknown hook '" + k + "'");
     return FS_EINVAL;
@@ -1043,6 +1045,34 @@ int fs_mdr_unrank(int64_t p, int k, int64_t rank, int32_t* features) {
     return FS_EINVAL;
   }
   mdr_unrank(p, k, rank, features);
+  return FS_OK;
+}
+
+int fs_mi_matrices(int backend, int device, const uint8_t* codes, const uint8_t* ycodes, int64_t n,
+                   int64_t p, int n_states, int unit, int n_jobs, double* relevance,
+                   double* redundancy, int32_t* counts_out) {
+  if (backend != FS_BACKEND_CPU && backend != FS_BACKEND_GPU) {
+    set_error("backend must be FS_BACKEND_CPU or FS_BACKEND_GPU");
+    return FS_EINVAL;
+  }
+  // the argument checks come before the device check: both backends reject
+  // the same calls the same way, with or without a device
+  int rc = mi_check(backend, codes, ycodes, n, p, n_states, unit, relevance);
+  if (rc != FS_OK) return rc;
+  if ((rc = check_backend(backend, device)) != FS_OK) return rc;
+  if (backend == FS_BACKEND_GPU)
+    return gpu::mi_matrices(device, codes, ycodes, n, p, n_states, unit, relevance, redundancy,
+                            counts_out);
+  return cpu::mi_matrices(codes, ycodes, n, p, n_states, unit, n_jobs, relevance, redundancy,
+                          counts_out);
+}
+
+int fs_mi_last_timing(double* ms4) {
+  if (!ms4) {
+    set_error("fs_mi_last_timing: NULL output");
+    return FS_EINVAL;
+  }
+  gpu::mi_last_timing(ms4);
   return FS_OK;
 }
 

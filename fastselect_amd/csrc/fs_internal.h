@@ -143,6 +143,7 @@ struct TestHooks {
   int64_t colsort_star = -1;   // 0: MultiSURF* split plans sort twice (binned correction + star sort)
   int64_t colsort_bins12 = 0;  // 1: 4096 bins at every n
   int64_t colsort_global = 0;  // 1: the large-n (device sort) route at every n
+  int64_t mi_tiles = 0;        // >= 1: tiles per launch of the mutual-information scan (fs_mi.hip)
 };
 TestHooks& test_hooks();
 

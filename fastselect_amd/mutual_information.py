@@ -1,0 +1,99 @@
+"""Discrete mutual information (reference: src/fast_select/mutual_information.py).
+
+``calculate_mi_matrices`` returns the relevance vector I(X_f; y) and the
+p x p redundancy matrix I(X_i; X_j) of integer-coded data;
+``calculate_mi_single_pair`` one value.  Both keep the reference's shape
+checks (mutual_information.py:128-129, 171-172) and ``_validate_discrete``
+(mutual_information.py:13-22), then make one call to ``fs_mi_matrices``, which
+replaces ``_batch_mi_cpu`` and ``_mi_pair_gpu_kernel``
+(mutual_information.py:49-115).
+
+Differences from the reference, on purpose:
+
+* backend='gpu' computes the whole matrix on the GPU.  The reference's GPU
+  path computes only the relevance there, with a kernel that strides the
+  samples by ``blockIdx`` and accumulates in float32
+  (mutual_information.py:84-90, 184-190), and hands the matrix to the CPU
+  (mutual_information.py:191-193).  Here both backends evaluate the float64
+  expressions of ``_mi_pair_cpu`` (mutual_information.py:31-46) on exact
+  integer tables.
+* More than 256 states is a ``ValueError``: codes travel as bytes.  The
+  reference's CPU path has no cap.
+* ``_mi_pair_cpu`` is ``@njit(fastmath=True)``, which lets LLVM reassociate its
+  float64 sums; no reference-produced fixture pins numba's own bits, so parity
+  with them is unpinned (as for MDR).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+
+_MAX_STATES_GPU = 32   # mutual_information.py:66
+_MAX_STATES = 256      # state codes are bytes at the native boundary
+
+
+def _validate_discrete(arr: np.ndarray, name: str) -> np.ndarray:
+    """Integer dtype and no negative entry (mutual_information.py:13-22)."""
+    if not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(
+            f"{name} must be an integer‑coded array (got {arr.dtype}). "
+            "Discretise continuous data before calling this function."
+        )
+    if arr.min() < 0:
+        raise ValueError(f"{name} contains negative values; expected 0..K‑1 codes.")
+    return arr
+
+
+def _choose_backend(backend: str, max_state: int) -> str:
+    """The reference's dispatch (mutual_information.py:137-154, 180-182):
+    'gpu' as asked, 'auto' on the GPU when a device is visible and the states
+    fit; 'gpu' never falls back."""
+    if max_state > _MAX_STATES:
+        raise ValueError(
+            f"at most {_MAX_STATES} states are supported (got {max_state}): "
+            "state codes are stored as bytes")
+    if backend == "auto":
+        return "gpu" if _lib.gpu_available() and max_state <= _MAX_STATES_GPU else "cpu"
+    if backend == "gpu":
+        if not _lib.gpu_available():
+            raise RuntimeError("backend='gpu' requested but no HIP device is visible")
+        if max_state > _MAX_STATES_GPU:
+            raise RuntimeError(
+                f"GPU backend supports ≤{_MAX_STATES_GPU} states (got {max_state}); "
+                "try backend='cpu'")
+        return "gpu"
+    if backend != "cpu":
+        raise ValueError("backend must be 'auto', 'cpu' or 'gpu'")
+    return "cpu"
+
+
+def calculate_mi_single_pair(x1, x2, *, backend="auto", unit="bit", n_jobs=-1, device=0) -> float:
+    """Mutual information I(x1; x2) of two integer-coded 1-D arrays
+    (mutual_information.py:117-155)."""
+    x1 = np.asarray(x1)
+    x2 = np.asarray(x2)
+    if x1.ndim != 1 or x2.ndim != 1 or x1.shape != x2.shape:
+        raise ValueError("x1 and x2 must be 1‑D arrays of equal length")
+    x1_d = _validate_discrete(x1.ravel(), "x1")
+    x2_d = _validate_discrete(x2.ravel(), "x2")
+    max_state = int(max(x1_d.max(), x2_d.max())) + 1
+    where = _choose_backend(backend, max_state)
+    rel, _ = _lib.mi_matrices(where, x1_d.reshape(-1, 1), x2_d, max_state, unit=unit,
+                              n_jobs=n_jobs, device=device)
+    return float(rel[0])
+
+
+def calculate_mi_matrices(X, y, *, backend="auto", unit="bit", n_jobs=-1, device=0):
+    """(relevance, redundancy) of integer-coded X (n x p) and y (n)
+    (mutual_information.py:158-196).  ``n_jobs`` and ``device`` are not
+    reference parameters."""
+    X = np.asarray(X)
+    y = np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1 or X.shape[0] != y.shape[0]:
+        raise ValueError("X must be 2‑D and y 1‑D with matching sample size")
+    X_d = _validate_discrete(X, "X")
+    y_d = _validate_discrete(y, "y")
+    max_state = int(max(X_d.max(), y_d.max())) + 1
+    where = _choose_backend(backend, max_state)
+    return _lib.mi_matrices(where, X_d, y_d, max_state, unit=unit, n_jobs=n_jobs, device=device)

@@ -116,7 +116,7 @@ FS_API int fs_get_accumulation(void);
  * ("ksplit", "q16", "sparse", "shards", "q16_guard_off", "thr_exact_all",
  * "exact_gather", "row_panel",
  * "rf_xlds", "rf_fcap", "ties_1w", "ties_coop", "rf_ref_replay", "ref_q16", "surf_f64",
- * "colsort_bins12", "colsort_global", "star_split", "colsort_star").  FS_EINVAL for an unknown name.  Not thread-safe
+ * "colsort_bins12", "colsort_global", "star_split", "colsort_star", "mi_tiles").  FS_EINVAL for an unknown name.  Not thread-safe
  * against concurrent scoring calls.
  */
 FS_API int fs_test_hook(const char* name, int64_t value);
@@ -547,6 +547,41 @@ FS_API int fs_mdr_combinations(int64_t p, int k, int64_t* count);
 /* rank -> the k ascending column indices of that combination, i.e.
  * all_combos[rank] of the reference (MDR.py:283), without the list. */
 FS_API int fs_mdr_unrank(int64_t p, int k, int64_t rank, int32_t* features);
+
+/* ---- mRMR: pairwise discrete mutual information -------------------------- */
+
+/*
+ * Relevance I(X_f; y) of every column and the p x p matrix of pairwise mutual
+ * information I(X_i; X_j) of integer-coded data.  Replaces _mi_pair_cpu and
+ * _batch_mi_cpu (mutual_information.py:25-63), _mi_pair_gpu_kernel
+ * (mutual_information.py:70-115) and the backend dispatch of
+ * calculate_mi_matrices (mutual_information.py:158-196), whose GPU path
+ * leaves the matrix to the CPU.
+ *   codes       [n][p] row-major state codes, 0..n_states-1
+ *   ycodes      [n] codes of the target, same range
+ *   unit        0 = bits, 1 = nats
+ *   n_jobs      CPU threads (-1 = all); ignored by the GPU backend
+ *   relevance   [p]
+ *   redundancy  [p][p] symmetric, zero diagonal; NULL: relevance only
+ *   counts_out  NULL, or [p][p][n_states][n_states] int32: for i < j the
+ *               contingency table of the pair (row = state of column i), else
+ *               zeros (sized by the caller; for tests and small jobs)
+ * A table cell is a popcount of two ANDed state bit-planes (exact integers,
+ * equal in both backends); the float64 expressions of _mi_pair_cpu follow in
+ * their written order (mutual_information.py:31-46), a pair once for i < j with
+ * the rows taken from column i, then mirrored.  The backends differ only
+ * through the host's and the device's log().  FS_EINVAL: n < 1 or n >= 2^31,
+ * p < 1, n_states outside 1..256, a code >= n_states, unit outside 0..1, more
+ * than 32 states on the GPU backend (the reference's _MAX_STATES_GPU), NULL
+ * codes / ycodes / relevance.  FS_EOOM when the matrices do not fit.
+ */
+FS_API int fs_mi_matrices(int backend, int device, const uint8_t* codes, const uint8_t* ycodes,
+                          int64_t n, int64_t p, int n_states, int unit, int n_jobs,
+                          double* relevance, double* redundancy, int32_t* counts_out);
+/* Milliseconds the calling thread's last GPU fs_mi_matrices spent on upload,
+ * pack, scan and download (HIP events; -1 where unavailable), for the
+ * benchmark tool. */
+FS_API int fs_mi_last_timing(double* ms4);
 
 #ifdef __cplusplus
 }
