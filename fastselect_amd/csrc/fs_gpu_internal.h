@@ -54,7 +54,7 @@ namespace gpu {
 constexpr int kRowcorrMaxSlices = 16;
 constexpr int kExRows = 8, kExJ = 4, kExChunk = kExJ;
 constexpr int kSWaves = 16;
-constexpr int kStreamEntries = (kTile / kSWaves) * kTile;
+constexpr int kTileWeights = kTile * kTile;  // floats of a tile in the sparse weight blocks (k_weights_sparse3)
 constexpr int64_t kXsSlack = 512;
 constexpr int kXcds = 8;
 
@@ -189,7 +189,7 @@ struct Plan {
   int2* tiles = nullptr;
   double* thr = nullptr;
   float* Wt = nullptr;          // dense pair weights (sparse == 0)
-  uint2* ent = nullptr;         // sparse pair-weight streams (sparse == 1)
+  float* wrow = nullptr;        // sparse pair weights, row-major per wave (sparse == 1)
   unsigned long long* nnz = nullptr;  // non-zero weights of the last pass 2
   bool nnz_valid = false;
   int sparse = 0;               // pass 2 over non-zero weights only

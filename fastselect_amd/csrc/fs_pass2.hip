@@ -70,15 +70,8 @@ __global__ __launch_bounds__(256) void k_weights(const double* __restrict__ D, i
 }
 
 // Sparse pair weights (pass 2 skips zero weights; MultiSURF: ~42% of the
-// pairs are near one of their two samples): k_weights_sparse2 / k_score_sparse2
+// pairs are near one of their two samples): k_weights_sparse3 / k_score_sparse3
 // below.  A workgroup of the sparse kernels has kSWaves waves.
-// entries a tile's streams may hold: 16 streams x 8 columns x 128 rows (both halves)
-// floats past xs's last spare row that a pass-2 B-row read may touch (the
-// widest feature block of k_score_sparse2)
-
-__device__ __forceinline__ uint32_t weight_bits(float w, bool last) {
-  return (__float_as_uint(w) & ~1u) | (last ? 1u : 0u);
-}
 
 // ---------------------------------------------------------------------------
 // Pass 2: weighted per-feature accumulation over owned tiles
@@ -227,73 +220,67 @@ __global__ __launch_bounds__(256) void k_score(const float* __restrict__ xs, int
 }
 
 // ---------------------------------------------------------------------------
-// Pass 2, sparse v2: 64-row half tiles, 8 features per lane
+// Pass 2, sparse v3: 64-row half tiles, 8 features per lane, row-major walk
 // ---------------------------------------------------------------------------
 // Grid as k_score (XCD-aware, segments of consecutive tiles), 16 waves per
-// workgroup (one workgroup per CU).  The round-1/2 form (v1, retired in
-// round 4) held a whole 128-row tile per wave, so a workgroup
-// kept 128 rows x 256 features (128 KB) in LDS and every entry fed 4
-// features per lane: the entry streams were re-read once per 256-feature
-// block (79 times at cfg4) and each scalar load of 8 entries covered 8 x 9
-// VALU.  v2 splits each tile into its two 64-row halves: a workgroup keeps 64 rows x
-// 512 features (the same 128 KB) and every entry feeds 8 features per lane --
-// one v_add_u32 address, two ds_read_b128, 8 x (v_sub_f32, v_fma_f32 |.|): 17
-// VALU per 8 pair-features instead of 18, half the scalar loads and half the
-// entry-stream reads per pair-feature (40 feature blocks at cfg4), and twice
-// the arithmetic behind every scalar load.  The B rows (the tile's columns)
-// are read once per half instead of once per tile; the two halves of a
-// (segment, feature block) sit in adjacent grid slots of one XCD, so the
-// second read is mostly an L2 hit.
+// workgroup (one workgroup per CU).  A workgroup keeps the 64 rows x 512
+// features of one tile half (128 KB) in LDS; wave w owns the columns jj = w,
+// w + 16, ... (8) of every tile of its segment and lane l scores 8 features
+// (F = 8; 4 in the 256-feature tail block).  v2 (retired) walked
+// each column's non-zero weights as a stream of (row offset, weight) entries
+// and re-read the 2 KB LDS row once per entry: one v_add_u32 and two
+// ds_read_b128 per 16 arithmetic VALU, an LDS 94% busy at full VALU rate.
+// v3 walks the same weights row by row: the 8 columns' B values stay in
+// registers for the whole tile half (64 VGPRs), a row is read from LDS once
+// and shared by the ~3.4 columns that have a weight in it (128 row reads per
+// stream instead of ~431 at cfg4), and the per-entry address add is gone --
+// 16 VALU per 8 pair-features.  The terms a wave adds for a tile are the same
+// as before, in row-major instead of column-major order.
 //
-// Stream (t, h, w) (k_weights_sparse2): the columns jj = w, w + 16, ... (8)
-// of owned tile t, each column's non-zero weights of the rows ii in
-// [64h, 64h + 64) as entries ((ii - 64h) * 2048, weight) in ascending ii --
-// 2048 = the byte stride of a row in the LDS block -- with NO padding: the
-// lowest mantissa bit of a weight is set on the last entry of its column and
-// clear elsewhere (a <= 1-ulp change, far below the 1e-5 bar), and an empty
-// column holds one (0, 0x1) entry (a denormal weight, zero for every
-// purpose).  Stream (t, h, w) starts at ent + ((t * 2 + h) * 16 + w) *
-// kStreamEntries2; 8 columns x 64 rows fill it at most.
+// Weights (k_weights_sparse3): a dense block per (owned tile t, half h, wave
+// w), W[t][h][w][r][c] as float, r = 0..63 the row of the half, c = 0..7 the
+// column jj = w + 16 c: 2 KB per stream, 64 KB per tile, every slot written
+// on every step.  No pair = +0.0 (never -0.0: the walk tests the bit
+// pattern).  Stream (t, h, w) starts at wrow + ((t * 2 + h) * 16 + w) *
+// kStreamWeights; the walk prefetches 128 bytes past a stream's end (the next
+// stream; the buffer ends with a spare tile).
 constexpr int kHalf = 64;
-constexpr int kRowBytes2 = 2048;                           // 64 lanes x 8 floats
-constexpr int kStreamEntries2 = (kTile / kSWaves) * kHalf;  // 512
-static_assert(kStreamEntries2 * 2 == kStreamEntries, "v2 streams reuse the v1 buffer size");
+constexpr int kWaveCols = kTile / kSWaves;                  // 8
+constexpr int kStreamWeights = kWaveCols * kHalf;           // 512
+static_assert(kStreamWeights * 2 * kSWaves == kTileWeights, "two halves x 16 streams per tile");
 
-__global__ __launch_bounds__(1024) void k_weights_sparse2(
+__global__ __launch_bounds__(1024) void k_weights_sparse3(
     const double* __restrict__ D, int64_t n, int64_t n_pad, int tiled, int2 win,
     const int2* __restrict__ tiles, const double* __restrict__ thr,
     const int32_t* __restrict__ lab,
     const double* __restrict__ counts, int algo, int use_star, double inv_sc, int64_t r_lo,
-    int64_t r_hi, uint2* __restrict__ ent, unsigned long long* __restrict__ nnz) {
+    int64_t r_hi, float* __restrict__ wrow, unsigned long long* __restrict__ nnz) {
   __shared__ int wave_nnz[kSWaves];
   const int2 tl = tiles[blockIdx.x];
   const int64_t i0 = (int64_t)tl.x * kTile, j0 = (int64_t)tl.y * kTile;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint2* out0 = ent + (((int64_t)blockIdx.x * 2 + 0) * kSWaves + wave) * kStreamEntries2;
-  uint2* out1 = ent + (((int64_t)blockIdx.x * 2 + 1) * kSWaves + wave) * kStreamEntries2;
-  const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
-  const uint32_t roff = (uint32_t)lane * (uint32_t)kRowBytes2;
-  int off0 = 0, off1 = 0, nz = 0;
-  for (int jj = wave; jj < kTile; jj += kSWaves) {
+  // lane = the row of the half: its 8 weights are 32 contiguous bytes
+  float* out0 = wrow + (((int64_t)blockIdx.x * 2 + 0) * kSWaves + wave) * kStreamWeights + lane * kWaveCols;
+  float* out1 = wrow + (((int64_t)blockIdx.x * 2 + 1) * kSWaves + wave) * kStreamWeights + lane * kWaveCols;
+  float v0[kWaveCols], v1[kWaveCols];
+  int nz = 0;
+#pragma unroll
+  for (int c = 0; c < kWaveCols; c++) {
+    const int jj = wave + kSWaves * c;
     const float w0 = pair_weight(D, n, n_pad, tiled, win, blockIdx.x, i0, j0, lane, jj,
                                  tl.x < tl.y || lane < jj, thr, lab, counts, algo, use_star,
                                  inv_sc, r_lo, r_hi);
     const float w1 = pair_weight(D, n, n_pad, tiled, win, blockIdx.x, i0, j0, lane + 64, jj,
                                  tl.x < tl.y || lane + 64 < jj, thr, lab, counts, algo, use_star,
                                  inv_sc, r_lo, r_hi);
-    const uint64_t m0 = __ballot(w0 != 0.0f), m1 = __ballot(w1 != 0.0f);
-    const int n0 = __popcll(m0), n1 = __popcll(m1);
-    // stream lengths (at least one entry: an empty column still ends)
-    const int p0 = n0 == 0 ? 1 : n0;
-    const int p1 = n1 == 0 ? 1 : n1;
-    const int e0 = __popcll(m0 & below), e1 = __popcll(m1 & below);
-    if (w0 != 0.0f) out0[off0 + e0] = make_uint2(roff, weight_bits(w0, e0 == p0 - 1));
-    if (w1 != 0.0f) out1[off1 + e1] = make_uint2(roff, weight_bits(w1, e1 == p1 - 1));
-    if (n0 + lane < p0) out0[off0 + n0 + lane] = make_uint2(0u, n0 + lane == p0 - 1 ? 1u : 0u);
-    if (n1 + lane < p1) out1[off1 + n1 + lane] = make_uint2(0u, n1 + lane == p1 - 1 ? 1u : 0u);
-    off0 += p0;
-    off1 += p1;
-    nz += n0 + n1;
+    v0[c] = w0 != 0.0f ? w0 : 0.0f;  // -0.0 -> +0.0
+    v1[c] = w1 != 0.0f ? w1 : 0.0f;
+    nz += __popcll(__ballot(w0 != 0.0f)) + __popcll(__ballot(w1 != 0.0f));
+  }
+#pragma unroll
+  for (int c = 0; c < kWaveCols; c += 4) {
+    *(float4*)(out0 + c) = make_float4(v0[c], v0[c + 1], v0[c + 2], v0[c + 3]);
+    *(float4*)(out1 + c) = make_float4(v1[c], v1[c + 1], v1[c + 2], v1[c + 3]);
   }
   if (lane == 0) wave_nnz[wave] = nz;
   __syncthreads();
@@ -304,47 +291,50 @@ __global__ __launch_bounds__(1024) void k_weights_sparse2(
   }
 }
 
-// Generic (plain HIP) walk of one v2 stream: F features per lane (8: chunks
+// The walk of one v3 stream in plain HIP: F features per lane (8: chunks
 // c = 0, 1 of the row, 4 each; 4: chunk 0 only), per-lane discrete flags.
 // Used for feature blocks holding discrete features; continuous blocks take
-// the generated loop of fs_sparse_asm.inc.
+// the generated loop of fs_sparse_asm.inc, which is this loop with wide
+// scalar weight loads, counted waits and a scalar test per weight.
 template <int F>
-__device__ __forceinline__ void sparse2_stream_generic(const float4* __restrict__ As,
-                                                       const uint2* __restrict__ e,
-                                                       const float* __restrict__ xb, int64_t bstride,
-                                                       int lane, const bool (&disc)[F],
-                                                       float (&acc)[F]) {
+__device__ __forceinline__ void sparse3_rows_generic(const float4* __restrict__ As,
+                                                     const float* __restrict__ wp,
+                                                     const float* __restrict__ xb, int64_t bstride,
+                                                     int lane, const bool (&disc)[F],
+                                                     float (&acc)[F]) {
   constexpr int C = F / 4;
-  float b[F];
-  int col = 0;
+  float b[kWaveCols][F];
 #pragma unroll
-  for (int c = 0; c < C; c++) {
-    const float4 v = *(const float4*)(xb + 256 * c);
-    b[4 * c] = v.x; b[4 * c + 1] = v.y; b[4 * c + 2] = v.z; b[4 * c + 3] = v.w;
-  }
-  for (int q = 0; q < kStreamEntries2; q++) {
-    const uint2 E = e[q];
-    const float w = __uint_as_float(E.y);
+  for (int j = 0; j < kWaveCols; j++)
 #pragma unroll
     for (int c = 0; c < C; c++) {
-      const float4 a = As[(E.x >> 4) + 64 * c + lane];
-      const float av[4] = {a.x, a.y, a.z, a.w};
+      const float4 v = *(const float4*)(xb + j * bstride + 256 * c);
+      b[j][4 * c] = v.x; b[j][4 * c + 1] = v.y; b[j][4 * c + 2] = v.z; b[j][4 * c + 3] = v.w;
+    }
+  float4 a[C], an[C];
 #pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int f = 4 * c + k;
-        acc[f] = disc[f] ? pair_term<true>(av[k], b[f], w, acc[f])
-                         : pair_term<false>(av[k], b[f], w, acc[f]);
+  for (int c = 0; c < C; c++) a[c] = As[64 * c + lane];
+  for (int r = 0; r < kHalf; r++) {
+    const int rn = (r + 1) & (kHalf - 1);  // requested before row r is consumed
+#pragma unroll
+    for (int c = 0; c < C; c++) an[c] = As[(rn * 2 + c) * 64 + lane];
+    float av[F];
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+      av[4 * c] = a[c].x; av[4 * c + 1] = a[c].y; av[4 * c + 2] = a[c].z; av[4 * c + 3] = a[c].w;
+    }
+#pragma unroll
+    for (int j = 0; j < kWaveCols; j++) {
+      const float w = wp[r * kWaveCols + j];  // wave-uniform
+      if (__float_as_uint(w) != 0u) {
+#pragma unroll
+        for (int f = 0; f < F; f++)
+          acc[f] = disc[f] ? pair_term<true>(av[f], b[j][f], w, acc[f])
+                           : pair_term<false>(av[f], b[j][f], w, acc[f]);
       }
     }
-    if (E.y & 1u) {  // last entry of the column
-      if (++col == kTile / kSWaves) break;
-      xb += bstride;
 #pragma unroll
-      for (int c = 0; c < C; c++) {
-        const float4 v = *(const float4*)(xb + 256 * c);
-        b[4 * c] = v.x; b[4 * c + 1] = v.y; b[4 * c + 2] = v.z; b[4 * c + 3] = v.w;
-      }
-    }
+    for (int c = 0; c < C; c++) a[c] = an[c];
   }
 }
 
@@ -358,9 +348,9 @@ __device__ __forceinline__ void sparse2_stream_generic(const float4* __restrict_
 // features f0 + 4l + k and (F = 8) f0 + 256 + 4l + k, k = 0..3; partials go
 // to spart[(seg * 2 + h) * PW + f].
 template <int F>
-__global__ __launch_bounds__(1024) void k_score_sparse2(
+__global__ __launch_bounds__(1024) void k_score_sparse3(
     const float* __restrict__ xs, int64_t PW, int64_t PC, const int2* __restrict__ tiles,
-    const uint2* __restrict__ ent, const int32_t* __restrict__ sched,
+    const float* __restrict__ wrow, const int32_t* __restrict__ sched,
     const int32_t* __restrict__ seg_off, const int2* __restrict__ units, int64_t f_base,
     double* __restrict__ spart) {
   constexpr int C = F / 4;
@@ -385,10 +375,8 @@ __global__ __launch_bounds__(1024) void k_score_sparse2(
   const bool fast = f_end <= PC;
   const uint32_t lds_lane = (uint32_t)(uintptr_t)As + (uint32_t)lane * 16u;
   const uint32_t glb_lane = (uint32_t)lane * 16u;
-  const uint32_t pf_lane = (uint32_t)lane * 32u;
   const int64_t bstride = kSWaves * PW;
   const uint32_t bstride_b = (uint32_t)(bstride * sizeof(float));
-  const uint32_t ncols = kTile / kSWaves;
   double s[F];
 #pragma unroll
   for (int q = 0; q < F; q++) s[q] = 0.0;
@@ -440,20 +428,17 @@ __global__ __launch_bounds__(1024) void k_score_sparse2(
     float acc[F];
 #pragma unroll
     for (int q = 0; q < F; q++) acc[q] = 0.0f;
-    const uint2* __restrict__ e = ent + ((t * 2 + h) * kSWaves + wave) * kStreamEntries2;
+    const float* __restrict__ wp = wrow + ((t * 2 + h) * kSWaves + wave) * kStreamWeights;
     const float* __restrict__ xb = xs + ((int64_t)tl.y * kTile + wave) * PW + f0;
     if (fast) {
-      const uint64_t eb = (uint64_t)(uintptr_t)e;
+      const uint64_t wb = (uint64_t)(uintptr_t)wp;
       const uint64_t bp = (uint64_t)(uintptr_t)xb;
-      // next-tile prefetch operands of the loop (the shipped loops are
-      // generated without the prefetch: tools/gen_sparse_asm.py pfn)
-      const uint64_t bpn = bp, enb = eb;
       if constexpr (F == 8) {
-        FS_SPARSE2_ASM_F8(acc, lds_lane, glb_lane, eb, bp, bstride_b, ncols, bpn, pf_lane, enb);
+        FS_SPARSE3_ASM_F8(acc, lds_lane, glb_lane, wb, bp, bstride_b);
       } else
-        FS_SPARSE2_ASM_F4(acc, lds_lane, glb_lane, eb, bp, bstride_b, ncols, bpn, pf_lane, enb);
+        FS_SPARSE3_ASM_F4(acc, lds_lane, glb_lane, wb, bp, bstride_b);
     } else {
-      sparse2_stream_generic<F>(As, e, xb + 4 * lane, bstride, lane, disc, acc);
+      sparse3_rows_generic<F>(As, wp, xb + 4 * lane, bstride, lane, disc, acc);
     }
 #pragma unroll
     for (int q = 0; q < F; q++) s[q] += (double)acc[q];
@@ -536,7 +521,7 @@ int reduce_segments(const double* part, int64_t nrows, int64_t PW, const int64_t
 // correction and the pass-2 segments (sized by the owned tiles and the
 // feature blocks), with the segment partials' buffer grown when needed.
 // plan_layout calls it, and plan_set_shard alone: re-targeting a plan to
-// Pass-2 schedule of the sparse kernels (k_score_sparse2).  The B operand of
+// Pass-2 schedule of the sparse kernels (k_score_sparse3).  The B operand of
 // a tile (its 128 column samples' values, 2 KB each per 512-feature block)
 // is read once per (tile, feature block, half): ~250 GB per launch at cfg4,
 // far more than L2 holds when the workgroups on an XCD all walk different
@@ -712,10 +697,10 @@ int run_weights(Plan* g, const double* counts, int algo, double inv_sc) {
   if (g->sparse) {
     FS_HIP(hipMemsetAsync(g->nnz, 0, sizeof(unsigned long long), g->stream));
     g->nnz_valid = true;
-    k_weights_sparse2<<<(unsigned)g->n_tiles, 64 * kSWaves, 0, g->stream>>>(
+    k_weights_sparse3<<<(unsigned)g->n_tiles, 64 * kSWaves, 0, g->stream>>>(
         g->D, Q.n, Q.n_pad, g->tiled, g->win, g->tiles, g->thr, g->lab, counts, algo,
-        star, inv_sc, g->r_lo, g->r_hi, g->ent, g->nnz);
-    return launch_check("k_weights_sparse2");
+        star, inv_sc, g->r_lo, g->r_hi, g->wrow, g->nnz);
+    return launch_check("k_weights_sparse3");
   }
   k_weights<<<(unsigned)g->n_tiles, 256, 0, g->stream>>>(g->D, Q.n, Q.n_pad, g->tiled, g->win,
                                                          g->tiles,
@@ -742,15 +727,15 @@ int run_pass2(Plan* g, double* scores_dev) {
     // F = 8 block is cheaper than two F = 4 ones -- cfg2, 448 features:
     // 0.24 -> 0.17 ms)
     if (g->nunits8 > 0) {
-      k_score_sparse2<8><<<(unsigned)g->nunits8, 64 * kSWaves, 0, g->stream>>>(
-          g->xs, Q.PW, Q.PC, g->tiles, g->ent, g->sched, g->seg_off, g->units8, 0, g->spart);
-      FS_TRY(launch_check("k_score_sparse2<8>"));
+      k_score_sparse3<8><<<(unsigned)g->nunits8, 64 * kSWaves, 0, g->stream>>>(
+          g->xs, Q.PW, Q.PC, g->tiles, g->wrow, g->sched, g->seg_off, g->units8, 0, g->spart);
+      FS_TRY(launch_check("k_score_sparse3<8>"));
     }
     if (g->nunits4 > 0) {
-      k_score_sparse2<4><<<(unsigned)g->nunits4, 64 * kSWaves, 0, g->stream>>>(
-          g->xs, Q.PW, Q.PC, g->tiles, g->ent, g->sched, g->seg_off, g->units4, g->f_tail,
+      k_score_sparse3<4><<<(unsigned)g->nunits4, 64 * kSWaves, 0, g->stream>>>(
+          g->xs, Q.PW, Q.PC, g->tiles, g->wrow, g->sched, g->seg_off, g->units4, g->f_tail,
           g->spart);
-      FS_TRY(launch_check("k_score_sparse2<4>"));
+      FS_TRY(launch_check("k_score_sparse3<4>"));
     }
   } else {
     k_score<<<(unsigned)(kXcds * seg_per_xcd * nfb), 256, 0, g->stream>>>(

@@ -76,8 +76,8 @@ static bool choose_star_split(const Prepared& P, int device) {
   return (double)P.n_pad * (double)P.PW * sizeof(float) <= 0.25 * (double)free_b;
 }
 
-// Pass 2 on the non-zero pair weights only (k_weights_sparse2 +
-// k_score_sparse2) or on every pair (k_weights + k_score).  Round 1's sparse
+// Pass 2 on the non-zero pair weights only (k_weights_sparse3 +
+// k_score_sparse3) or on every pair (k_weights + k_score).  Round 1's sparse
 // loop cost ~1.7x the dense one per evaluated pair; the v2 loop (round 4)
 // ~1.3x, so it pays below ~75% density.  MultiSURF weighs the ~42% of pairs
 // near one of their samples, SURF the ~62% (cfg5: the whole step 179.4 ->
@@ -333,12 +333,13 @@ static int setup_shard(Plan* g, const std::vector<int32_t>& bi, const std::vecto
   } else if (Q.algo != ALGO_RELIEFF && !g->sparse) {
     rc = dalloc(g, &g->Wt, (size_t)(g->n_tiles + 1) * kTile * kTile);
   } else if (g->sparse) {
-    // One spare tile: k_score_sparse prefetches two groups past the end of a
-    // stream.  Zeroed once, so such reads (and stream tails never written)
-    // hold in-range row offsets.
-    const size_t count = (size_t)(g->n_tiles + 1) * kSWaves * kStreamEntries;
-    if (!(rc = dalloc(g, &g->ent, count)) && !(rc = dalloc(g, &g->nnz, 1)) &&
-        hipMemsetAsync(g->ent, 0, sizeof(uint2) * count, g->stream) != hipSuccess)
+    // 64 KB per tile (k_weights_sparse3 writes every slot on every step)
+    // and one spare tile: k_score_sparse3 prefetches the weights of a step
+    // past the end of a stream (never used; zeroed once all the same).
+    const size_t count = (size_t)(g->n_tiles + 1) * kTileWeights;
+    if (!(rc = dalloc(g, &g->wrow, count)) && !(rc = dalloc(g, &g->nnz, 1)) &&
+        hipMemsetAsync(g->wrow + (size_t)g->n_tiles * kTileWeights, 0,
+                       sizeof(float) * kTileWeights, g->stream) != hipSuccess)
       rc = FS_EHIP;
   }
   if (!rc && g->ksplit > 1)
@@ -368,7 +369,7 @@ int plan_set_shard(Plan* g, int rank, int world) {
   g->D = g->Dpart = nullptr;
   g->D_alloc = nullptr;
   g->Wt = nullptr;
-  g->ent = nullptr;
+  g->wrow = nullptr;
   g->tiles = nullptr;
   g->rspart = nullptr;
   g->nnz = nullptr;

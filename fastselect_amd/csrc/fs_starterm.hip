@@ -9,7 +9,7 @@
 //   MultiSURF*  w_ij = [near] (hit ? -1/H_i : +2/M'_i)  -  [miss] / M'_i
 //   SURF*       w_ij = [near] (hit ? -2 : +2)           +  (hit ? +1 : -1)
 //
-// The near part is the sparse pass 2 (k_weights_sparse2 with use_star = 2:
+// The near part is the sparse pass 2 (k_weights_sparse3 with use_star = 2:
 // cfg5 holds 41.7% near pairs for MultiSURF, 62.4% for SURF, against 62%
 // and 100% non-zero star weights; profiles/r06/near_density.txt).  The
 // all-pairs part of feature f is

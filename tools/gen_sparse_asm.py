@@ -240,8 +240,8 @@ def gen(name="FS_SPARSE_STREAM_ASM", no_ds=False, same_stream=False, feats=4, sp
 
 
 HEADER = """// Generated by tools/gen_sparse_asm.py -- do not edit by hand.
-// Inner loops of k_score_sparse2 for continuous feature blocks (see the
-// generator's docstring for the layout, the pipeline and the fixed registers).
+// Inner loops of k_score_sparse3 for continuous feature blocks (see V3_DOC in
+// the generator for the layout, the pipeline and the fixed registers).
 """
 
 # ---------------------------------------------------------------------------
@@ -1374,17 +1374,156 @@ def gen_v2seg(name, lead=3):
 """
 
 
+# ---------------------------------------------------------------------------
+# v3 (shipped): row-major walk of a dense weight block, one LDS row read
+# shared by the wave's 8 columns
+# ---------------------------------------------------------------------------
+V3_DOC = """
+Sparse v3 loop (k_score_sparse3).  A wave's weights of one 64-row half tile
+are a dense block W[r][c] of floats (r = 0..63, c = 0..7: column jj = w + 16 c;
++0.0 = no pair; 2 KB, k_weights_sparse3), walked row by row: the A row is read
+from LDS ONCE per row (F/4 ds_read_b128) and shared by the up to 8 columns
+with a weight in that row, where v2 re-read it once per entry.  The B values
+of all 8 columns stay in VGPRs for the whole stream (8 x F/4
+global_load_dwordx4 at its start).  Per (row, column): s_cmp_eq_u32 w, 0 and
+a scalar branch over the block of F x (v_sub_f32 into scratch -- not in
+place: the other columns reuse the row --, v_fma_f32 acc += w * |d|): 2F VALU
+per F pair-features, no address arithmetic (rows are immediate ds_read offsets
+from one address register that advances once per 8 rows).
+A step is 4 rows = 32 weights (two s_load_dwordx16 into one of two SGPR sets,
+requested at the start of the previous step) and starts with the only
+lgkmcnt(0).  Row r + 1 is requested (into the other slot of a two-slot ring)
+before row r is consumed and waited with a counted lgkmcnt (LDS completes in
+order; scalar loads in flight only make the wait stricter).  The body is 8
+rows (2 steps); the read after a body's last row goes to the next body's
+first row, or back to row 0 after the 8th body (never past the LDS block).
+The first row's column blocks wait for their own B loads with counted vmcnt
+(free once the counter has reached 0) and the row ends with vmcnt(0), so a
+stream starts on its first weighted column's arrival.  The weight prefetch of the last step reads the 128 bytes
+after the stream (the next stream, or the buffer's spare tile).
+Registers: v24.. B (8 x F), then the ring (2 x F), the scratch (F) and the
+row address; s[20:21] B row pointer, s22 body counter, s24 weight offset,
+s25 temporary, s[26:27] stream base, s28 address step, s36..s99 two weight
+sets.
+"""
+
+
+def gen_v3(name, F=8):
+    R = F // 4                       # ds_read_b128 per row
+    NC = 8                           # columns per wave
+    SET = [36, 68]
+    B0 = 24
+    RING = B0 + NC * F
+    TMP = RING + 2 * F
+    VA = TMP + F
+    ROWB = 2048                      # bytes of a row in the LDS block
+    BPTR, CNT, OFF, T, BASE, STEP = 20, 22, 24, 25, 26, 28
+    BODY = 8                         # rows per unrolled body
+
+    def slot(r):
+        return RING + F * (r % 2)
+
+    def read(i):
+        # row i + 1 of the body (i = BODY - 1: the next body's first row)
+        a = slot(i + 1)
+        off = (i + 1) * ROWB if i + 1 < BODY else 0
+        L_ = [f"v_add_u32 v{VA}, s{STEP}, v{VA}"] if i + 1 == BODY else []
+        if F == 8:
+            L_.append(f"ds_read_b128 v[{a + 4}:{a + 7}], v{VA} offset:{off + 1024}")
+        L_.append(f"ds_read_b128 v[{a}:{a + 3}], v{VA}" + (f" offset:{off}" if off else ""))
+        return L_
+
+    lab = [0]
+
+    def block(i, c, w):
+        a, b = slot(i), B0 + F * c
+        lab[0] += 1
+        L_ = [f"s_cmp_eq_u32 s{w}, 0", f"s_cbranch_scc1 {100 + lab[0]}f"]
+        if i == 0:  # the stream's first row: column c's B loads (later bodies: already 0)
+            L_.append(f"s_waitcnt vmcnt({(NC - 1 - c) * R})")
+        L_ += [f"v_sub_f32 v{TMP + f}, v{a + f}, v{b + f}" for f in range(F)]
+        L_ += [f"v_fma_f32 %[acc{f}], s{w}, |v{TMP + f}|, %[acc{f}]" for f in range(F)]
+        L_.append(f"{100 + lab[0]}:")
+        return L_
+
+    def step(x):
+        k, o = x % 2, 1 - x % 2
+        S = ["s_waitcnt lgkmcnt(0)",
+             f"s_load_dwordx16 s[{SET[o]}:{SET[o] + 15}], s[{BASE}:{BASE + 1}], s{OFF}",
+             f"s_add_u32 s{T}, s{OFF}, 64",
+             f"s_load_dwordx16 s[{SET[o] + 16}:{SET[o] + 31}], s[{BASE}:{BASE + 1}], s{T}",
+             f"s_add_u32 s{OFF}, s{OFF}, 128"]
+        for j in range(4):
+            i = 4 * x + j
+            S += read(i)
+            if j:  # the step's first row landed with the lgkmcnt(0) above
+                S.append(f"s_waitcnt lgkmcnt({R})")
+            for c in range(NC):
+                S += block(i, c, SET[k] + NC * j + c)
+            if i == 0:  # columns without a weight in the first row waited for nothing
+                S.append("s_waitcnt vmcnt(0)")
+        return S
+
+    def bload(c):
+        d = B0 + F * c
+        L_ = [f"global_load_dwordx4 v[{d}:{d + 3}], %[glb_lane], s[{BPTR}:{BPTR + 1}]"]
+        if F == 8:
+            L_.append(f"global_load_dwordx4 v[{d + 4}:{d + 7}], %[glb_lane], s[{BPTR}:{BPTR + 1}] offset:1024")
+        return L_
+
+    lines = [f"s_mov_b64 s[{BASE}:{BASE + 1}], %[wb]",
+             f"s_load_dwordx16 s[{SET[0]}:{SET[0] + 15}], s[{BASE}:{BASE + 1}], 0x0",
+             f"s_load_dwordx16 s[{SET[0] + 16}:{SET[0] + 31}], s[{BASE}:{BASE + 1}], 0x40",
+             f"s_mov_b32 s{OFF}, 128",
+             f"s_mov_b64 s[{BPTR}:{BPTR + 1}], %[bp]"]
+    for c in range(NC):
+        lines += bload(c)
+        if c + 1 < NC:
+            lines += [f"s_add_u32 s{BPTR}, s{BPTR}, %[bstride]", f"s_addc_u32 s{BPTR + 1}, s{BPTR + 1}, 0"]
+    lines += [f"s_mov_b32 s{CNT}, 0",
+              f"v_mov_b32 v{VA}, %[lds_lane]"]
+    a = slot(0)
+    if F == 8:
+        lines.append(f"ds_read_b128 v[{a + 4}:{a + 7}], v{VA} offset:1024")
+    lines.append(f"ds_read_b128 v[{a}:{a + 3}], v{VA}")
+    lines += ["7:",
+              f"s_add_u32 s{CNT}, s{CNT}, 1",
+              f"s_mov_b32 s{STEP}, 0x{BODY * ROWB:x}",
+              f"s_cmp_lt_u32 s{CNT}, {64 // BODY}",
+              # after the last body: back to row 0, not past the LDS block
+              f"s_cselect_b32 s{STEP}, s{STEP}, 0x{(-(64 - BODY) * ROWB) & 0xffffffff:x}"]
+    for x in range(BODY // 4):
+        lines += step(x)
+    lines += [f"s_cmp_lt_u32 s{CNT}, {64 // BODY}", "s_cbranch_scc1 7b",
+              "s_waitcnt vmcnt(0) lgkmcnt(0)"]
+    body = "\n".join(f'      "{l}\\n"  \\' for l in lines)
+    vclob = ", ".join(f'"v{i}"' for i in range(B0, VA + 1))
+    named = set()
+    for l in lines:
+        for lo, hi in re.findall(r"(?<![a-z_])s\[?(\d+)(?::(\d+)\])?", l):
+            named.update(range(int(lo), int(hi or lo) + 1))
+    sclob = ", ".join(f'"s{i}"' for i in sorted(named))
+    return f"""#define {name}(acc_, lds_lane_, glb_lane_, wb_, bp_, bstride_)  \\
+  asm volatile(  \\
+{body}
+      : {", ".join(f'[acc{i}] "+v"(acc_[{i}])' for i in range(F))}  \\
+      : [lds_lane] "v"(lds_lane_), [glb_lane] "v"(glb_lane_), [wb] "s"(wb_), [bp] "s"(bp_),  \\
+        [bstride] "s"(bstride_)  \\
+      : {vclob},  \\
+        {sclob}, "scc", "memory")
+"""
+
+
 if __name__ == "__main__":
-    # The product uses the v2 loops only (k_score_sparse2; round 4 retired the
-    # round-1/2 v1 loop and its A/B variants -- the functions above stay for
-    # the microbenchmarks under tools/ubench and their logs in profiles/).
+    # The product uses the v3 loops only (k_score_sparse3): the v2 loops
+    # (entry streams, one row read per entry) were retired for the row-major
+    # walk, the round-1/2 v1 loop in round 4 -- the functions above stay for
+    # the record, the microbenchmarks under tools/ubench and their logs in
+    # profiles/.
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "fastselect_amd", "csrc",
                         "fs_sparse_asm.inc")
     text = HEADER
-    text += "\n" + gen_v2("FS_SPARSE2_ASM_F8", F=8, lead=3, pfn=False)
-    text += "\n" + gen_v2("FS_SPARSE2_ASM_F4", F=4, lead=6, pfn=False)
+    text += "\n" + gen_v3("FS_SPARSE3_ASM_F8", F=8)
+    text += "\n" + gen_v3("FS_SPARSE3_ASM_F4", F=4)
     open(path, "w").write(text)
     print("wrote", os.path.normpath(path))
-    # (round 4's clock-stamp variant of the F = 8 loop, gen_v2(tprof=True),
-    # fed a profiling build that is no longer part of the library sources:
-    # its measurements are in profiles/r04/pass2_prio.txt)
