@@ -154,6 +154,7 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "colsort_bins12") h.colsort_bins12 = value;
   else if (k == "colsort_global") h.colsort_global = value;
   else if (k == "mi_tiles") h.mi_tiles = value;
+  else if (k == "list_cap") h.list_cap = value;
   else {
     set_error("fs_test_hook: unknown hook '" + k + "'");
     return FS_EINVAL;

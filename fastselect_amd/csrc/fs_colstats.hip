@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/fastselect_amd.h"
+#include "fs_devmem.h"
 #include "fs_internal.h"
 
 namespace fs {
@@ -145,7 +146,7 @@ int column_minmax(const void* dx, int x_is_f64, int64_t n, int64_t p, void* hmin
   const size_t esz = x_is_f64 ? 8 : 4;
   int64_t rows_per_chunk = 0, nchunks = 0;
   minmax_grid(n, rows_per_chunk, nchunks);
-  void* buf = nullptr;  // [nchunks][p] min, [nchunks][p] max, [p] min, [p] max
+  char* b = nullptr;  // [nchunks][p] min, [nchunks][p] max, [p] min, [p] max
   const size_t part = (size_t)nchunks * p * esz;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) {
@@ -153,9 +154,9 @@ int column_minmax(const void* dx, int x_is_f64, int64_t n, int64_t p, void* hmin
     set_error("column ranges: hipGetDevice failed");
     return FS_EHIP;
   }
-  if (int rc = dev_alloc(&buf, 2 * part + 2 * (size_t)p * esz, dev)) return rc;
+  DevArena mem(dev);  // freed on return, after the stream is synchronised
+  if (int rc = mem.alloc(&b, 2 * part + 2 * (size_t)p * esz)) return rc;
   hipError_t e;
-  char* b = (char*)buf;
   launch_minmax(dx, x_is_f64, n, p, rows_per_chunk, nchunks, b, b + part, b + 2 * part,
                 b + 2 * part + p * esz, s);
   e = hipGetLastError();
@@ -164,7 +165,6 @@ int column_minmax(const void* dx, int x_is_f64, int64_t n, int64_t p, void* hmin
   if (e == hipSuccess)
     e = hipMemcpyAsync(hmax, b + 2 * part + p * esz, (size_t)p * esz, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  dev_free(buf);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     set_error(std::string("column ranges: ") + hipGetErrorString(e));
@@ -189,7 +189,7 @@ int column_stats(const void* x, int x_is_f64, int64_t n, int64_t p, int64_t cap,
   const size_t esz = x_is_f64 ? 8 : 4;
   int64_t rows_per_chunk = 0, nchunks = 0;
   minmax_grid(n, rows_per_chunk, nchunks);
-  void *dx = nullptr, *pmin = nullptr, *pmax = nullptr, *dmin = nullptr, *dmax = nullptr;
+  char *dx = nullptr, *pmin = nullptr, *pmax = nullptr, *dmin = nullptr, *dmax = nullptr;
   int64_t* dcnt = nullptr;
   hipStream_t s = nullptr;
   int rc = FS_OK;
@@ -204,12 +204,13 @@ int column_stats(const void* x, int x_is_f64, int64_t n, int64_t p, int64_t cap,
     fail("hipStreamCreate", e);
   // a staged copy of x (fs_stage_x) is read in place, else x is uploaded
   const void* sx = staged_lookup(x, n, p, x_is_f64, device);
-  if (rc == FS_OK && !sx) rc = dev_alloc((void**)&dx, (size_t)n * p * esz, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&pmin, (size_t)nchunks * p * esz, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&pmax, (size_t)nchunks * p * esz, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dmin, (size_t)p * esz, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dmax, (size_t)p * esz, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dcnt, (size_t)p * 8, device);
+  DevArena mem(device);
+  if (rc == FS_OK && !sx) rc = mem.alloc(&dx, (size_t)n * p * esz);
+  if (rc == FS_OK) rc = mem.alloc(&pmin, (size_t)nchunks * p * esz);
+  if (rc == FS_OK) rc = mem.alloc(&pmax, (size_t)nchunks * p * esz);
+  if (rc == FS_OK) rc = mem.alloc(&dmin, (size_t)p * esz);
+  if (rc == FS_OK) rc = mem.alloc(&dmax, (size_t)p * esz);
+  if (rc == FS_OK) rc = mem.alloc(&dcnt, (size_t)p);
   if (rc == FS_OK &&
       !sx && (e = hipMemcpyAsync(dx, x, (size_t)n * p * esz, hipMemcpyHostToDevice, s)) != hipSuccess)
     fail("hipMemcpy H2D", e);
@@ -239,8 +240,7 @@ int column_stats(const void* x, int x_is_f64, int64_t n, int64_t p, int64_t cap,
     fail("hipMemcpy D2H", e);
   if (rc == FS_OK && (e = hipStreamSynchronize(s)) != hipSuccess) fail("column statistics", e);
   if (s) (void)hipStreamSynchronize(s);
-  for (void* q : {dx, pmin, pmax, dmin, dmax, (void*)dcnt})
-    if (q) dev_free(q);
+  mem.release();
   if (s) (void)hipStreamDestroy(s);
   return rc;
 }

@@ -91,15 +91,16 @@ bool exchange_parts(DevGroup& G, int r, hipStream_t st, hipEvent_t ev, const dou
 // X on every device of a devices= call, moved over the host link once: thread
 // r uploads its 1/N of the rows into a full-size buffer on its device, then
 // copies the other threads' row ranges from their devices (xGMI peer copies;
-// a repeated ordinal copies within the device).  *buf receives the buffer
-// (caller frees it after a barrier that follows the last peer copy).
-bool distribute_x(DevGroup& G, int r, const void* x, size_t row_bytes, int64_t n, void** buf,
-                  hipStream_t st, hipEvent_t ev, int& rc) {
+// a repeated ordinal copies within the device).  *buf receives the buffer,
+// a block of `mem` (the caller releases it after a barrier that follows the
+// last peer copy).
+bool distribute_x(DevGroup& G, int r, const void* x, size_t row_bytes, int64_t n, DevArena& mem,
+                  char** buf, hipStream_t st, hipEvent_t ev, int& rc) {
   const int dev = G.devices[r];
   *buf = nullptr;
-  if (!rc) rc = dev_alloc(buf, row_bytes * (size_t)n, dev);
+  if (!rc) rc = mem.alloc(buf, row_bytes * (size_t)n);
   auto lo = [&](int k) { return n * k / G.N; };
-  if (!rc && hipMemcpyAsync((char*)*buf + row_bytes * lo(r), (const char*)x + row_bytes * lo(r),
+  if (!rc && hipMemcpyAsync(*buf + row_bytes * lo(r), (const char*)x + row_bytes * lo(r),
                             row_bytes * (size_t)(lo(r + 1) - lo(r)), hipMemcpyHostToDevice,
                             st) != hipSuccess) {
     (void)hipGetLastError();
@@ -114,7 +115,7 @@ bool distribute_x(DevGroup& G, int r, const void* x, size_t row_bytes, int64_t n
   for (int k = 0; k < G.N && !rc; k++) {
     if (k == r || lo(k + 1) == lo(k)) continue;
     if (hipStreamWaitEvent(st, G.ready[k], 0) != hipSuccess ||
-        hipMemcpyPeerAsync((char*)*buf + row_bytes * lo(k), dev,
+        hipMemcpyPeerAsync(*buf + row_bytes * lo(k), dev,
                            (const char*)G.send[k] + row_bytes * lo(k), G.devices[k],
                            row_bytes * (size_t)(lo(k + 1) - lo(k)), st) != hipSuccess) {
       (void)hipGetLastError();
@@ -175,7 +176,8 @@ int multisurf_run_devices(const Prepared& P, const void* x, const int* devices, 
     // per exchange: this thread's part, the gathered parts, the sum
     double *rs_p = nullptr, *cnt_p = nullptr, *sc_p = nullptr, *gath = nullptr;
     double *rs = nullptr, *cnt = nullptr, *sc = nullptr, *tmp = nullptr;
-    void* xbuf = nullptr;
+    DevArena xmem(devices[r]);
+    char* xbuf = nullptr;
     uint64_t staged = 0;
     hipStream_t xs_st = nullptr;
     hipEvent_t evs[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -183,21 +185,23 @@ int multisurf_run_devices(const Prepared& P, const void* x, const int* devices, 
     for (auto& e : evs)
       if (!rc && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = FS_EHIP;
     if (!rc && hipStreamCreateWithFlags(&xs_st, hipStreamNonBlocking) != hipSuccess) rc = FS_EHIP;
-    bool ok = distribute_x(G, r, x, sizeof(float) * (size_t)P.p_in, n, &xbuf, xs_st, evs[0], rc);
+    bool ok = distribute_x(G, r, x, sizeof(float) * (size_t)P.p_in, n, xmem, &xbuf, xs_st,
+                           evs[0], rc);
     if (ok && !rc) rc = stage_x_device(devices[r], x, xbuf, 0, n, P.p_in, &staged);
     if (ok && !rc) rc = plan_create(&g, P, x, 0, devices[r], r, W, 0);
     if (staged) unstage_x(staged);
     if (ok && !rc) rc = plan_set_rows(g, r_lo, r_hi);
     const int64_t glen = (int64_t)N * std::max<int64_t>(3 * n, nk);
-    if (ok && !rc && ((rc = dalloc(g, &rs_p, 3 * n)) || (rc = dalloc(g, &cnt_p, 2 * n)) ||
-                      (rc = dalloc(g, &sc_p, nk)) || (rc = dalloc(g, &rs, 3 * n)) ||
-                      (rc = dalloc(g, &cnt, 2 * n)) || (rc = dalloc(g, &sc, nk)) ||
-                      (rc = dalloc(g, &gath, glen)) ||
-                      (rc = dalloc(g, &tmp, std::max<int64_t>(3 * n, nk)))))
+    DevArena* M = g ? &g->mem_plan : nullptr;
+    if (ok && !rc && ((rc = M->alloc(&rs_p, 3 * n)) || (rc = M->alloc(&cnt_p, 2 * n)) ||
+                      (rc = M->alloc(&sc_p, nk)) || (rc = M->alloc(&rs, 3 * n)) ||
+                      (rc = M->alloc(&cnt, 2 * n)) || (rc = M->alloc(&sc, nk)) ||
+                      (rc = M->alloc(&gath, glen)) ||
+                      (rc = M->alloc(&tmp, std::max<int64_t>(3 * n, nk)))))
       ;
     // every peer has copied its rows of xbuf (the barrier after the copies)
     // and the plan holds its own copy: free it
-    if (xbuf) dev_free(xbuf);
+    xmem.release();
     hipStream_t st = g ? g->stream : nullptr;
     auto exch = [&](int which) {
       double* part = which == 0 ? rs_p : which == 1 ? cnt_p : sc_p;
@@ -295,7 +299,8 @@ int rows_run_devices(const Prepared& P, const void* x, const int* devices, int n
   auto worker = [&](int r) {
     const int64_t lo = std::max(r_lo, (b0 + nb * r / N) * kTile);
     const int64_t hi = std::min(r_hi, (b0 + nb * (r + 1) / N) * kTile);
-    void* xbuf = nullptr;
+    DevArena xmem(devices[r]);
+    char* xbuf = nullptr;
     uint64_t staged = 0;
     hipStream_t st = nullptr;
     hipEvent_t ev = nullptr;
@@ -305,13 +310,14 @@ int rows_run_devices(const Prepared& P, const void* x, const int* devices, int n
       rc = FS_EHIP;
     // X once over the host link: 1/N of the rows per device, the rest by
     // peer copies, registered as this thread's staged X for the plans
-    const bool ok = distribute_x(G, r, x, (x_f64 ? 8 : 4) * (size_t)P.p_in, P.n, &xbuf, st, ev, rc);
+    const bool ok =
+        distribute_x(G, r, x, (x_f64 ? 8 : 4) * (size_t)P.p_in, P.n, xmem, &xbuf, st, ev, rc);
     if (ok && !rc) rc = stage_x_device(devices[r], x, xbuf, x_f64, P.n, P.p_in, &staged);
     if (ok && !rc && hi > lo)
       rc = P.algo == ALGO_RELIEFF ? relieff_run(P, x, devices[r], lo, hi, parts[r].data())
                                   : surf_run(P, x, devices[r], lo, hi, parts[r].data());
     if (staged) unstage_x(staged);
-    if (xbuf) dev_free(xbuf);
+    xmem.release();
     if (ok) G.bar.arrive(rc, rc ? std::string(fs_last_error()) : std::string());
     if (st) (void)hipStreamDestroy(st);
     if (ev) (void)hipEventDestroy(ev);

@@ -1,7 +1,8 @@
 // fs_gpu_internal.h -- what the GPU backend's translation units share: the
 // Plan (one scoring job's device state), the device helpers the kernels use,
-// the launch / allocation helpers and the entry points each unit offers the
-// others.  One unit per stage of the pipeline:
+// the launch helpers and the entry points each unit offers the others; the
+// owners of device memory are in fs_devmem.h.  One unit per stage of the
+// pipeline:
 //
 //   fs_gpu_mem.hip   devices, the device block cache, pinned host staging
 //   fs_pass1.hip     k_quantize, k_dist, row moments, mean correction glue,
@@ -36,6 +37,7 @@
 #include <vector>
 
 #include "../../include/fastselect_amd.h"
+#include "fs_devmem.h"
 #include "fs_internal.h"
 
 namespace fs {
@@ -132,9 +134,20 @@ __device__ __forceinline__ int64_t d_rd(int tiled, int2 win, int64_t n_pad, int6
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
+// Device memory of a Plan has one of two owners (fs_devmem.h).  Blocks that
+// live and die together sit in one of four arenas, named at each allocation:
+// mem_plan (sized by n: as long as the plan), mem_layout (sized by the feature
+// layout: until the next plan_layout), mem_shard (sized by the owned tiles:
+// until the next plan_set_shard) and mem_call (one plan_score call).  A buffer
+// that grows on demand is a DevBuf member: reserve() synchronises the streams
+// it is given, frees the old block and allocates the new size.  Kernels take
+// the raw pointer (.p) and capacity (.cap).  plan_destroy synchronises the
+// plan's streams; destroying the Plan then frees all of it.
 struct Plan {
+  explicit Plan(int dev) : device(dev) {}
   Prepared P;
-  int device = 0, rank = 0, world = 1;
+  const int device;
+  int rank = 0, world = 1;
   int x_is_f64 = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
@@ -147,7 +160,7 @@ struct Plan {
   hipStream_t side2 = nullptr;
   hipEvent_t ev_star = nullptr;
   int64_t nb = 0, n_tiles = 0, seg_len = 1, nseg = 1;
-  int64_t nsegpart = 1;         // rows of spart (nseg, or 2 * nseg for the v2 sparse pass)
+  int64_t nsegpart = 1;         // rows of spart (nseg, or 2 * nseg sparse: one per half)
   int ksplit = 1;               // pass-1 K-split parts of the tail tiles (k_dist)
   int64_t kfull = 0;            // tiles k_dist computes whole (the rest are split)
   int use_q16 = 0;              // pass 1 on packed 16-bit continuous operands
@@ -158,8 +171,7 @@ struct Plan {
   double2* rspart = nullptr;    // per owned tile row-moment partials [tiles][256]
   double* Dpart = nullptr;      // (ksplit - 1) partial distance planes
   int key_shift = 8;             // colsort_key shift of the current scale
-  void* colsort_scratch = nullptr;  // large-n route of colsort_terms
-  size_t colsort_scratch_bytes = 0;
+  DevBuf<char> colsort_scratch{device};  // large-n route of colsort_terms (its stream: run_colsort)
   // device buffers
   void* x = nullptr;            // X on the device: the plan's own, or a staged copy
   const void* x_staged = nullptr;  // the staged copy x reads (staged_acquire), released by plan_destroy
@@ -201,44 +213,36 @@ struct Plan {
   float* xsT = nullptr;
   double* alpha = nullptr;
   double* tcol = nullptr;
-  double* spart = nullptr;       // pass-2 segment partials (own block, shard_segments)
-  size_t spart_cap = 0;           // doubles of spart
+  DevBuf<double> spart{device};   // pass-2 segment partials (shard_segments)
   // sparse pass-2 schedule (build_sparse_schedule): tile order, segment
-  // offsets and the unit tables of the F = 8 / F = 4 launches (own blocks)
+  // offsets and the unit tables of the F = 8 / F = 4 launches
   std::vector<int2> h_tiles;      // the owned tiles (host copy of `tiles`)
-  int32_t* sched = nullptr;
-  int32_t* seg_off = nullptr;
-  int2* units8 = nullptr;
-  int2* units4 = nullptr;
-  size_t sched_cap = 0;           // int32 slots of `sched` + `seg_off` (one block)
-  size_t units_cap = 0;           // int2 slots of units8 + units4 (one block)
+  DevBuf<int32_t> sched{device};  // the tile order, then the segment offsets
+  int32_t* seg_off = nullptr;     // inside sched
+  DevBuf<int2> units8{device};    // the F = 8 units, then the F = 4 ones
+  int2* units4 = nullptr;         // inside units8
   int64_t nunits8 = 0, nunits4 = 0, nfb8 = 0, nfb4 = 0, f_tail = 0;
   // exact thresholds of uncertain rows (exact_thresholds)
   unsigned int* unc = nullptr;  // [n_pad] row flags
   int32_t* urows = nullptr;     // [n_pad + 1] flagged rows in index order, then their count
-  double2* uparts = nullptr;    // [thr_rows][nchunk] exact row-moment partials
-  size_t uparts_cap = 0;        // double2 slots of uparts
+  DevBuf<double2> uparts{device};  // [thr_rows][nchunk] exact row-moment partials
   int thr_rows = kExactThrRows; // rows fixed at most: exact_thr_rows(n) (thr_exact_all test hook: all)
   bool thr_all = false;
   int32_t n_exact_thr = 0;      // rows whose threshold the last select recomputed (-1: too many)
   // ambiguous-pair refinement
-  int2* list = nullptr;
-  int64_t list_cap = 0;
-  double* pair_part = nullptr;  // k_exact_pairs_rows' per-pair sums between feature chunks
-  int64_t pair_part_cap = 0;
+  DevBuf<int2> list{device};
+  DevBuf<double> pair_part{device};  // k_exact_pairs_rows' per-pair sums between feature chunks
   unsigned long long* list_count = nullptr;
   int64_t n_refined = 0;
   int64_t n_tie_rows = 0;      // ReliefF rows re-ordered by k_rf_ties
-  void* sort_scratch = nullptr;  // pair-list sort (fs_sort.hip)
-  size_t sort_scratch_bytes = 0;
+  DevBuf<char> sort_scratch{device};  // pair-list sort (fs_sort.hip)
   // ev[0..1] distance kernel, ev[2..3] score kernel(s) / ReliefF selection +
   // update, ev[4..5] ReliefF's first k_rf_select launch (plan_kernel_ms)
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  std::vector<void*> owned;         // buffers sized by n (live as long as the plan)
-  std::vector<void*> owned_layout;  // buffers sized by the feature layout (PW)
-  std::vector<void*> scratch;       // buffers of one plan_score call
-  std::vector<void*> owned_shard;   // buffers sized by the owned tiles (plan_set_shard)
-  int alloc_target = 0;             // dalloc target: 0 owned, 1 owned_layout, 2 scratch, 3 shard
+  DevArena mem_plan{device};    // buffers sized by n (live as long as the plan)
+  DevArena mem_layout{device};  // buffers sized by the feature layout (PW)
+  DevArena mem_shard{device};   // buffers sized by the owned tiles (plan_set_shard)
+  DevArena mem_call{device};    // buffers of one plan_score call
   bool row_mode = false;
   // the row guard's quantised operands and mean correction are the first
   // step's (one plan over every continuous column): pass 1 takes them
@@ -259,29 +263,13 @@ struct Plan {
   uint8_t* kblk = nullptr;
   uint64_t* masks = nullptr;
   int32_t* bcnt = nullptr;
-  float* temp = nullptr;        // the reference's temp rows [rows][Kp] (own block)
-  size_t temp_cap = 0;
+  DevBuf<float> temp{device};   // the reference's temp rows [rows][Kp]
   int64_t ref_rows = -1;        // rows of temp the last plan_ref_pass2 / _temp wrote (-1: none)
   bool ref_defer = false;       // ReliefF reference order: stop at the temp rows (plan_ref_temp)
-  float* rkeys = nullptr;       // ReliefF neighbour keys (own block)
-  size_t rkeys_cap = 0;
+  DevBuf<float> rkeys{device};  // ReliefF neighbour keys
   bool ref_seeded = false;      // ReliefF: the column sums continue from the sums buffer
-  double* risk_dev = nullptr;   // plan_decision_guard's result (owned, allocated on first use)
+  double* risk_dev = nullptr;   // plan_decision_guard's result (mem_plan, allocated on first use)
 };
-
-template <typename T>
-int dalloc(Plan* g, T** p, size_t count) {
-  void* q = nullptr;
-  if (count == 0) count = 1;
-  if (int rc = dev_alloc(&q, count * sizeof(T), g->device)) return rc;
-  (g->alloc_target == 1   ? g->owned_layout
-   : g->alloc_target == 2 ? g->scratch
-   : g->alloc_target == 3 ? g->owned_shard
-                          : g->owned)
-      .push_back(q);
-  *p = (T*)q;
-  return FS_OK;
-}
 
 #define FS_TRY(expr)              \
   do {                            \

@@ -247,16 +247,17 @@ int mdr_scan(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* 
   if (rc == FS_OK && (e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess)
     fail("hipStreamCreate", e);
   const size_t plane_words = (size_t)W * 3 * (size_t)p;
-  if (rc == FS_OK) rc = dev_alloc((void**)&dx, (size_t)n * p, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dperm, L.perm.size() * 4, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dseg, L.seg_off.size() * 4, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dtc, (size_t)F * 8, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dtn, (size_t)F * 8, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dplanes, plane_words * 4, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dpbits, nslots * 4, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dprank, nslots * 8, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dbad, 4, device);
-  if (rc == FS_OK && ba_out) rc = dev_alloc((void**)&dba, (size_t)F * count * 4, device);
+  DevArena mem(device);  // freed on return, after the stream is synchronised
+  if (rc == FS_OK) rc = mem.alloc(&dx, (size_t)n * p);
+  if (rc == FS_OK) rc = mem.alloc(&dperm, L.perm.size());
+  if (rc == FS_OK) rc = mem.alloc(&dseg, L.seg_off.size());
+  if (rc == FS_OK) rc = mem.alloc(&dtc, (size_t)F);
+  if (rc == FS_OK) rc = mem.alloc(&dtn, (size_t)F);
+  if (rc == FS_OK) rc = mem.alloc(&dplanes, plane_words);
+  if (rc == FS_OK) rc = mem.alloc(&dpbits, nslots);
+  if (rc == FS_OK) rc = mem.alloc(&dprank, nslots);
+  if (rc == FS_OK) rc = mem.alloc(&dbad, 1);
+  if (rc == FS_OK && ba_out) rc = mem.alloc(&dba, (size_t)F * count);
   up(dx, x, (size_t)n * p, "upload of X");
   up(dperm, L.perm.data(), L.perm.size() * 4, "upload of the sample order");
   up(dseg, L.seg_off.data(), L.seg_off.size() * 4, "upload of the segments");
@@ -342,9 +343,6 @@ int mdr_scan(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* 
       memcpy(&best_ba[i], &bits, 4);
       best_rank[i] = rank;
     }
-  for (void* q : {(void*)dx, (void*)dperm, (void*)dseg, (void*)dtc, (void*)dtn, (void*)dplanes,
-                  (void*)dpbits, (void*)dprank, (void*)dbad, (void*)dba})
-    if (q) dev_free(q);
   if (s) (void)hipStreamDestroy(s);
   return rc;
 }

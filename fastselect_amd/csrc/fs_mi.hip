@@ -288,14 +288,15 @@ int mi_matrices(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t
     fail("hipStreamCreate", e);
   for (int k = 0; k < 5 && rc == FS_OK; k++)
     if ((e = hipEventCreate(&ev[k])) != hipSuccess) fail("hipEventCreate", e);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dx, (size_t)n * p, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dy, (size_t)n, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dplanes, plane_words * 4, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dkcol, (size_t)P1 * 4, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&drel, (size_t)p * 8, device);
-  if (rc == FS_OK) rc = dev_alloc((void**)&dbad, 4, device);
-  if (rc == FS_OK && nred) rc = dev_alloc((void**)&dred, nred * 8, device);
-  if (rc == FS_OK && ncnt) rc = dev_alloc((void**)&dcnt, ncnt * 4, device);
+  DevArena mem(device);  // freed on return, after the stream is synchronised
+  if (rc == FS_OK) rc = mem.alloc(&dx, (size_t)n * p);
+  if (rc == FS_OK) rc = mem.alloc(&dy, (size_t)n);
+  if (rc == FS_OK) rc = mem.alloc(&dplanes, plane_words);
+  if (rc == FS_OK) rc = mem.alloc(&dkcol, (size_t)P1);
+  if (rc == FS_OK) rc = mem.alloc(&drel, (size_t)p);
+  if (rc == FS_OK) rc = mem.alloc(&dbad, 1);
+  if (rc == FS_OK && nred) rc = mem.alloc(&dred, nred);
+  if (rc == FS_OK && ncnt) rc = mem.alloc(&dcnt, ncnt);
 
   mark(0);
   if (rc == FS_OK && ((e = hipMemcpyAsync(dx, codes, (size_t)n * p, hipMemcpyHostToDevice, s)) !=
@@ -372,9 +373,6 @@ int mi_matrices(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t
       if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) g_mi_ms[k] = ms;
     }
   (void)hipGetLastError();
-  for (void* q : {(void*)dx, (void*)dy, (void*)dplanes, (void*)dkcol, (void*)drel, (void*)dbad,
-                  (void*)dred, (void*)dcnt})
-    if (q) dev_free(q);
   for (hipEvent_t v : ev)
     if (v) (void)hipEventDestroy(v);
   if (s) (void)hipStreamDestroy(s);

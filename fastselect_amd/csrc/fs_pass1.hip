@@ -896,9 +896,10 @@ int calibrate_band(Plan* g) {
   int2* dpr = nullptr;
   double* dqs = nullptr;
   double2* derr = nullptr;
-  int rc = dev_alloc((void**)&dpr, sizeof(int2) * S, g->device);
-  if (!rc) rc = dev_alloc((void**)&dqs, sizeof(double) * qs.size(), g->device);
-  if (!rc) rc = dev_alloc((void**)&derr, sizeof(double2) * S, g->device);
+  DevArena tmp(g->device);
+  int rc = tmp.alloc(&dpr, (size_t)S);
+  if (!rc) rc = tmp.alloc(&dqs, qs.size());
+  if (!rc) rc = tmp.alloc(&derr, (size_t)S);
   std::vector<double2> err((size_t)S);
   if (!rc && (hipMemcpyAsync(dpr, pr.data(), sizeof(int2) * S, hipMemcpyHostToDevice,
                              g->stream) != hipSuccess ||
@@ -921,9 +922,7 @@ int calibrate_band(Plan* g) {
                              g->stream) != hipSuccess ||
               hipStreamSynchronize(g->stream) != hipSuccess))
     rc = FS_EHIP;
-  if (dpr) dev_free(dpr);
-  if (dqs) dev_free(dqs);
-  if (derr) dev_free(derr);
+  tmp.release();
   if (rc) {
     (void)hipGetLastError();
     if (rc == FS_EHIP) set_error("band calibration: HIP call failed");
@@ -987,19 +986,11 @@ static int run_colsort(Plan* g, int64_t c_lo, int64_t c_hi, hipStream_t s) {
       set_error("mean correction: column sort scratch query failed");
       return FS_EHIP;
     }
-    if (need > g->colsort_scratch_bytes) {
-      const int tgt = g->alloc_target;
-      g->alloc_target = 0;
-      char* p = nullptr;
-      const int rc = dalloc(g, &p, need);
-      g->alloc_target = tgt;
-      if (rc) return rc;
-      g->colsort_scratch = p;
-      g->colsort_scratch_bytes = need;
-    }
+    hipStream_t users[2] = {g->stream, s};  // earlier calls ran on either
+    FS_TRY(g->colsort_scratch.reserve(need, 0, users, 2));
   }
   return colsort_terms(g->xqT, g->epsT, Q.n, Q.n_pad, c_lo, c_hi, Q.q16, g->key_shift,
-                       g->colsort_scratch, g->colsort_scratch_bytes, s)
+                       g->colsort_scratch.p, g->colsort_scratch.cap, s)
              ? FS_EHIP
              : FS_OK;
 }
@@ -1086,7 +1077,8 @@ int row_guard(Plan* g) {
     return FS_OK;
   }
   double* corr = g->corr;
-  if (!reuse) FS_TRY(dev_alloc((void**)&corr, sizeof(double) * Q.n_pad, g->device));
+  DevArena tmp(g->device);
+  if (!reuse) FS_TRY(tmp.alloc(&corr, (size_t)Q.n_pad));
   dim3 gq((unsigned)(Q.PW / 64), (unsigned)(Q.n_pad / 64));
   int rc = FS_OK;
   if (g->x_is_f64)
@@ -1102,7 +1094,7 @@ int row_guard(Plan* g) {
   if (!rc) rc = run_rowcorr(g, 0, Q.pc, corr, g->stream);
   std::vector<double> h;
   if (!rc) rc = copy_corr(g, corr, h);
-  if (!reuse) dev_free(corr);
+  tmp.release();
   if (rc) return rc;
   bool switched = false;
   FS_TRY(row_guard_decide(g, h, &switched));

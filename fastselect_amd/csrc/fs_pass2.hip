@@ -180,9 +180,6 @@ __device__ __forceinline__ void score_tiles(const float* __restrict__ xs, int64_
 // one segment's pair weights (30 tiles x 64 KB) in that XCD's L2 instead of
 // ~8 segments thrashing it; the 1-D grid has 8 * max_x(segments of x) * nfb
 // slots, the few beyond nseg exit at once.
-// row blocks per group of the sparse pass-2 schedule (build_sparse_schedule;
-// 16 / kSchedRows feature blocks per block of units)
-
 __global__ __launch_bounds__(256) void k_score(const float* __restrict__ xs, int64_t PW,
                                                int64_t PC, const int2* __restrict__ tiles,
                                                const float* __restrict__ Wt, int64_t n_tiles,
@@ -517,10 +514,6 @@ int reduce_segments(const double* part, int64_t nrows, int64_t PW, const int64_t
   return launch_check("k_reduce");
 }
 
-// Shard part of a plan's layout: this rank's continuous columns of the mean
-// correction and the pass-2 segments (sized by the owned tiles and the
-// feature blocks), with the segment partials' buffer grown when needed.
-// plan_layout calls it, and plan_set_shard alone: re-targeting a plan to
 // Pass-2 schedule of the sparse kernels (k_score_sparse3).  The B operand of
 // a tile (its 128 column samples' values, 2 KB each per 512-feature block)
 // is read once per (tile, feature block, half): ~250 GB per launch at cfg4,
@@ -547,21 +540,8 @@ int reduce_segments(const double* part, int64_t nrows, int64_t PW, const int64_t
 #ifndef FS_SCHED_UNITS
 #define FS_SCHED_UNITS 32
 #endif
-constexpr int kSchedRows = FS_SCHED_ROWS;
-constexpr int kSchedFb = FS_SCHED_UNITS / kSchedRows;
-
-static int ensure_dev(Plan* g, void** buf, size_t* cap, size_t bytes) {
-  if (bytes <= *cap) return FS_OK;
-  if (*buf) {
-    FS_HIP(hipStreamSynchronize(g->stream));
-    dev_free(*buf);
-    *buf = nullptr;
-    *cap = 0;
-  }
-  FS_TRY(dev_alloc(buf, bytes, g->device));
-  *cap = bytes;
-  return FS_OK;
-}
+constexpr int kSchedRows = FS_SCHED_ROWS;                 // row blocks per group
+constexpr int kSchedFb = FS_SCHED_UNITS / kSchedRows;  // feature blocks per block of units
 
 static int build_sparse_schedule(Plan* g) {
   const Prepared& Q = g->P;
@@ -620,17 +600,21 @@ static int build_sparse_schedule(Plan* g) {
   if (sched.empty()) sched.push_back(0);
   const size_t ns = sched.size() + seg_off.size();
   const size_t nu = std::max<size_t>(1, u8.size() + u4.size());
-  FS_TRY(ensure_dev(g, (void**)&g->sched, &g->sched_cap, ns * sizeof(int32_t)));
-  FS_TRY(ensure_dev(g, (void**)&g->units8, &g->units_cap, nu * sizeof(int2)));
-  g->seg_off = g->sched + sched.size();
-  g->units4 = g->units8 + u8.size();
-  FS_TRY(h2d(g, g->sched, sched.data(), sched.size()));
+  FS_TRY(g->sched.reserve(ns, 0, &g->stream, 1));
+  FS_TRY(g->units8.reserve(nu, 0, &g->stream, 1));
+  g->seg_off = g->sched.p + sched.size();
+  g->units4 = g->units8.p + u8.size();
+  FS_TRY(h2d(g, g->sched.p, sched.data(), sched.size()));
   FS_TRY(h2d(g, g->seg_off, seg_off.data(), seg_off.size()));
-  if (!u8.empty()) FS_TRY(h2d(g, g->units8, u8.data(), u8.size()));
+  if (!u8.empty()) FS_TRY(h2d(g, g->units8.p, u8.data(), u8.size()));
   if (!u4.empty()) FS_TRY(h2d(g, g->units4, u4.data(), u4.size()));
   return FS_OK;
 }
 
+// Shard part of a plan's layout: this rank's continuous columns of the mean
+// correction and the pass-2 segments (sized by the owned tiles and the
+// feature blocks), with the segment partials' buffer grown when needed.
+// plan_layout calls it, and plan_set_shard alone: re-targeting a plan to
 // another tile shard keeps the feature layout, its tables and its band
 // calibration (none of them depends on the shard).
 int shard_segments(Plan* g) {
@@ -665,20 +649,7 @@ int shard_segments(Plan* g) {
   if (g->sparse) FS_TRY(build_sparse_schedule(g));  // its own segments (g->nseg)
   // partial rows per segment: one per half with the sparse streams
   g->nsegpart = g->sparse ? 2 * g->nseg : g->nseg;
-  const size_t need = (size_t)g->nsegpart * Q.PW;
-  if (need > g->spart_cap) {
-    if (g->spart) {
-      FS_HIP(hipStreamSynchronize(g->stream));
-      dev_free(g->spart);
-      g->spart = nullptr;
-      g->spart_cap = 0;
-    }
-    void* q = nullptr;
-    FS_TRY(dev_alloc(&q, need * sizeof(double), g->device));
-    g->spart = (double*)q;
-    g->spart_cap = need;
-  }
-  return FS_OK;
+  return g->spart.reserve((size_t)g->nsegpart * Q.PW, 0, &g->stream, 1);
 }
 
 // Pair weights of the owned tiles in the form pass 2 reads (dense or sparse).
@@ -717,7 +688,7 @@ int run_pass2(Plan* g, double* scores_dev) {
   FS_HIP(hipMemsetAsync(scores_dev, 0, sizeof(double) * Q.n_kept, g->stream));
   if (add && Q.algo == ALGO_SURF) FS_HIP(hipStreamWaitEvent(g->stream, g->ev_join, 0));
   if (g->n_tiles == 0) {
-    if (add) return reduce_segments(g->spart, 0, Q.PW, g->out_pos, scores_dev, g->stream, add);
+    if (add) return reduce_segments(g->spart.p, 0, Q.PW, g->out_pos, scores_dev, g->stream, add);
     return FS_OK;
   }
   FS_HIP(hipEventRecord(g->ev[2], g->stream));
@@ -728,22 +699,22 @@ int run_pass2(Plan* g, double* scores_dev) {
     // 0.24 -> 0.17 ms)
     if (g->nunits8 > 0) {
       k_score_sparse3<8><<<(unsigned)g->nunits8, 64 * kSWaves, 0, g->stream>>>(
-          g->xs, Q.PW, Q.PC, g->tiles, g->wrow, g->sched, g->seg_off, g->units8, 0, g->spart);
+          g->xs, Q.PW, Q.PC, g->tiles, g->wrow, g->sched.p, g->seg_off, g->units8.p, 0, g->spart.p);
       FS_TRY(launch_check("k_score_sparse3<8>"));
     }
     if (g->nunits4 > 0) {
       k_score_sparse3<4><<<(unsigned)g->nunits4, 64 * kSWaves, 0, g->stream>>>(
-          g->xs, Q.PW, Q.PC, g->tiles, g->wrow, g->sched, g->seg_off, g->units4, g->f_tail,
-          g->spart);
+          g->xs, Q.PW, Q.PC, g->tiles, g->wrow, g->sched.p, g->seg_off, g->units4, g->f_tail,
+          g->spart.p);
       FS_TRY(launch_check("k_score_sparse3<4>"));
     }
   } else {
     k_score<<<(unsigned)(kXcds * seg_per_xcd * nfb), 256, 0, g->stream>>>(
-        g->xs, Q.PW, Q.PC, g->tiles, g->Wt, g->n_tiles, g->seg_len, g->nseg, nfb, g->spart);
+        g->xs, Q.PW, Q.PC, g->tiles, g->Wt, g->n_tiles, g->seg_len, g->nseg, nfb, g->spart.p);
     FS_TRY(launch_check("k_score"));
   }
   FS_HIP(hipEventRecord(g->ev[3], g->stream));
-  k_reduce<<<(unsigned)((Q.PW + 63) / 64), 1024, 0, g->stream>>>(g->spart, g->nsegpart, Q.PW,
+  k_reduce<<<(unsigned)((Q.PW + 63) / 64), 1024, 0, g->stream>>>(g->spart.p, g->nsegpart, Q.PW,
                                                                    g->out_pos, add, scores_dev);
   return launch_check("k_reduce");
 }
@@ -756,13 +727,8 @@ int run_pass2(Plan* g, double* scores_dev) {
 // float32 sums, not yet divided by n).
 int ref_masks(Plan* g) {
   const Prepared& Q = g->P;
-  if (!g->masks) {  // the plan's own masks, on first use
-    const int at = g->alloc_target;
-    g->alloc_target = 0;
-    const int rc = dalloc(g, &g->masks, (size_t)ref_mask_words(g));
-    g->alloc_target = at;
-    FS_TRY(rc);
-  }
+  // the plan's own masks, on first use
+  if (!g->masks) FS_TRY(g->mem_plan.alloc(&g->masks, (size_t)ref_mask_words(g)));
   return refacc::multisurf_masks(g->D, Q.n, Q.n_pad, g->tiles, g->n_tiles, g->thr, g->lab,
                                  Q.use_star, g->masks, g->stream);
 }
@@ -771,16 +737,8 @@ int ref_masks(Plan* g) {
 // steps and grown on demand.
 int ref_temp(Plan* g, int64_t rows, float** out) {
   const size_t need = (size_t)std::max<int64_t>(rows, 1) * (size_t)g->Kp;
-  if (need > g->temp_cap) {
-    if (g->temp) dev_free(g->temp);
-    g->temp = nullptr;
-    g->temp_cap = 0;
-    void* p = nullptr;
-    FS_TRY(dev_alloc(&p, need * sizeof(float), g->device));
-    g->temp = (float*)p;
-    g->temp_cap = need;
-  }
-  *out = g->temp;
+  FS_TRY(g->temp.reserve(need, 0, &g->stream, 1));
+  *out = g->temp.p;
   return FS_OK;
 }
 
@@ -799,10 +757,7 @@ int surf_ref(Plan* g, double* sums) {
     return FS_OK;
   }
   uint64_t* m = nullptr;
-  g->alloc_target = 2;  // scratch of this plan_score
-  const int rc = dalloc(g, &m, (size_t)rows * (Q.n_pad / 64) * 4);
-  g->alloc_target = 0;
-  FS_TRY(rc);
+  FS_TRY(g->mem_call.alloc(&m, (size_t)rows * (Q.n_pad / 64) * 4));
   float* temp = nullptr;
   FS_TRY(ref_temp(g, rows, &temp));
   FS_HIP(hipEventRecord(g->ev[2], g->stream));
@@ -885,7 +840,7 @@ int plan_ref_sums(Plan* g, const double* init, double* sums) {
     else
       FS_HIP(hipMemsetAsync(sums, 0, sizeof(double) * Q.n_kept, g->stream));
   } else {
-    FS_TRY(refacc::column_sums(g->temp, g->ref_rows, g->Kp, Q.n_kept, init, sums, g->stream));
+    FS_TRY(refacc::column_sums(g->temp.p, g->ref_rows, g->Kp, Q.n_kept, init, sums, g->stream));
   }
   if (g->own_stream) FS_HIP(hipStreamSynchronize(g->stream));
   return FS_OK;

@@ -11,15 +11,6 @@ void plan_destroy(Plan* g) {
   trace_mark("kernels (to sync)");
   if (g->side) (void)hipStreamSynchronize(g->side);
   if (g->side2) (void)hipStreamSynchronize(g->side2);
-  for (void* q : g->owned) dev_free(q);
-  for (void* q : g->owned_layout) dev_free(q);
-  for (void* q : g->scratch) dev_free(q);
-  for (void* q : g->owned_shard) dev_free(q);
-  if (g->spart) dev_free(g->spart);
-  if (g->temp) dev_free(g->temp);
-  if (g->rkeys) dev_free(g->rkeys);
-  if (g->sched) dev_free(g->sched);
-  if (g->units8) dev_free(g->units8);
   if (g->x_staged) staged_release(g->x_staged);
   for (auto& e : g->ev) event_put(g->device, e, true);
   event_put(g->device, g->ev_fork, false);
@@ -28,7 +19,7 @@ void plan_destroy(Plan* g) {
   stream_put(g->device, g->side);
   if (g->side2) stream_put(g->device, g->side2);
   if (g->own_stream) stream_put(g->device, g->stream);
-  delete g;
+  delete g;  // its arenas and buffers: every stream that used them is synchronised
   trace_mark("plan: free");
 }
 
@@ -128,19 +119,15 @@ static int ref_layout(Plan* g) {
     dsc[k] = Q.disc_in[col] ? 1 : 0;
     if (dsc[k]) blk[k / blk_w] = 1;
   }
-  g->alloc_target = 1;
   g->xk = nullptr;
   g->xk64 = nullptr;
+  DevArena& M = g->mem_layout;
   int rc;
-  if ((rc = surf ? dalloc(g, &g->xk64, (size_t)Q.n_pad * g->Kp)
-                 : dalloc(g, &g->xk, (size_t)Q.n_pad * g->Kp)) ||
-      (rc = dalloc(g, &g->kcol, Q.n_kept)) || (rc = dalloc(g, &g->krecip, g->Kp)) ||
-      (rc = dalloc(g, &g->kdisc, g->Kp)) || (rc = dalloc(g, &g->kblk, g->Kp / blk_w))) {
-    g->alloc_target = 0;
-    return rc;
-  }
-  g->alloc_target = 0;
-  if ((rc = h2d(g, g->kcol, Q.kept_col.data(), Q.n_kept)) ||
+  if ((rc = surf ? M.alloc(&g->xk64, (size_t)Q.n_pad * g->Kp)
+                 : M.alloc(&g->xk, (size_t)Q.n_pad * g->Kp)) ||
+      (rc = M.alloc(&g->kcol, Q.n_kept)) || (rc = M.alloc(&g->krecip, g->Kp)) ||
+      (rc = M.alloc(&g->kdisc, g->Kp)) || (rc = M.alloc(&g->kblk, g->Kp / blk_w)) ||
+      (rc = h2d(g, g->kcol, Q.kept_col.data(), Q.n_kept)) ||
       (rc = h2d(g, g->krecip, rec.data(), rec.size())) ||
       (rc = h2d(g, g->kdisc, dsc.data(), dsc.size())) ||
       (rc = h2d(g, g->kblk, blk.data(), blk.size())))
@@ -162,17 +149,7 @@ static int size_exact_rows(Plan* g) {
   if (Q.algo != ALGO_MULTISURF) return FS_OK;
   g->thr_rows = (int)(g->thr_all ? Q.n : exact_thr_rows(Q.n, Q.pc + Q.pd));
   const int64_t nchunk = (Q.n + kExChunk - 1) / kExChunk;
-  const size_t need = (size_t)g->thr_rows * nchunk;
-  if (need <= g->uparts_cap) return FS_OK;
-  if (g->uparts) {
-    g->owned.erase(std::remove(g->owned.begin(), g->owned.end(), (void*)g->uparts),
-                   g->owned.end());
-    dev_free(g->uparts);
-    g->uparts = nullptr;
-  }
-  FS_TRY(dalloc(g, &g->uparts, need));
-  g->uparts_cap = need;
-  return FS_OK;
+  return g->uparts.reserve((size_t)g->thr_rows * nchunk, 0, &g->stream, 1);
 }
 
 int plan_layout(Plan* g) {
@@ -181,8 +158,7 @@ int plan_layout(Plan* g) {
   FS_HIP(hipStreamSynchronize(g->stream));
   if (g->side) FS_HIP(hipStreamSynchronize(g->side));
   if (g->side2) FS_HIP(hipStreamSynchronize(g->side2));
-  for (void* q : g->owned_layout) dev_free(q);
-  g->owned_layout.clear();
+  g->mem_layout.release();
   int rc;
   Q.q16 = g->use_q16;
   if (!Q.ranges_ready) {
@@ -216,26 +192,25 @@ int plan_layout(Plan* g) {
     return FS_EINVAL;
   }
   g->key_shift = colsort_key_shift(Q.qmax);
-  g->alloc_target = 1;
+  DevArena& M = g->mem_layout;
   rc = FS_OK;
-  if ((rc = dalloc(g, &g->src_col, Q.PW)) || (rc = dalloc(g, &g->out_pos, Q.PW)) ||
-      (rc = dalloc(g, &g->off, Q.PW)) || (rc = dalloc(g, &g->qs, Q.PW)) ||
-      (rc = dalloc(g, &g->scl, Q.PW)) || (rc = dalloc(g, &g->scl32, Q.PW)) ||
-      (rc = dalloc(g, &g->dtab_off, Q.PW + 1)) ||
-      (rc = dalloc(g, &g->dtab, Q.dtab.size())) ||
+  if ((rc = M.alloc(&g->src_col, Q.PW)) || (rc = M.alloc(&g->out_pos, Q.PW)) ||
+      (rc = M.alloc(&g->off, Q.PW)) || (rc = M.alloc(&g->qs, Q.PW)) ||
+      (rc = M.alloc(&g->scl, Q.PW)) || (rc = M.alloc(&g->scl32, Q.PW)) ||
+      (rc = M.alloc(&g->dtab_off, Q.PW + 1)) ||
+      (rc = M.alloc(&g->dtab, Q.dtab.size())) ||
       // xs: two spare rows (the pass-2 B prefetch runs up to two rows past a
       // tile) plus kXsSlack floats: the asm loop of a last, partial feature
       // block reads a whole block width of each B row, past the end of the
       // last row when PW is narrower than the block
-      (rc = dalloc(g, &g->xs, (size_t)(Q.n_pad + 2) * Q.PW + kXsSlack)) ||
-      (g->star_split && ((rc = dalloc(g, &g->xsT, (size_t)Q.PW * Q.n_pad)) ||
-                         (rc = dalloc(g, &g->tcol, Q.PW))))) {
+      (rc = M.alloc(&g->xs, (size_t)(Q.n_pad + 2) * Q.PW + kXsSlack)) ||
+      (g->star_split && ((rc = M.alloc(&g->xsT, (size_t)Q.PW * Q.n_pad)) ||
+                         (rc = M.alloc(&g->tcol, Q.PW))))) {
   } else if (Q.algo == ALGO_SURF) {
     // its operands follow the route the calibration picks (below)
-  } else if ((rc = dalloc(g, &g->xqT, (size_t)Q.PW * Q.n_pad)) == FS_OK) {
-    rc = dalloc(g, &g->epsT, (size_t)Q.PW * Q.n_pad);
+  } else if ((rc = M.alloc(&g->xqT, (size_t)Q.PW * Q.n_pad)) == FS_OK) {
+    rc = M.alloc(&g->epsT, (size_t)Q.PW * Q.n_pad);
   }
-  g->alloc_target = 0;
   if (rc) return rc;
   if ((rc = shard_segments(g))) return rc;
   std::vector<double> qs(Q.PW, 0.0);
@@ -256,11 +231,9 @@ int plan_layout(Plan* g) {
   if (Q.ref_accum && (rc = ref_layout(g))) return rc;
   if ((rc = calibrate_band(g))) return rc;
   if (Q.algo == ALGO_SURF) {  // integer (u32) or float64 feature-major operands
-    g->alloc_target = 1;
-    rc = g->surf_int ? dalloc(g, &g->xqT, (size_t)Q.PW * Q.n_pad)
-                     : dalloc(g, &g->xT64, (size_t)Q.PW * Q.n_pad);
-    g->alloc_target = 0;
-    if (rc) return rc;
+    if ((rc = g->surf_int ? M.alloc(&g->xqT, (size_t)Q.PW * Q.n_pad)
+                          : M.alloc(&g->xT64, (size_t)Q.PW * Q.n_pad)))
+      return rc;
   }
   if ((rc = row_guard(g))) return rc;
   if (g->calib[5] != 0.0 && (rc = apply_operand_width(g))) return rc;
@@ -320,32 +293,31 @@ static int setup_shard(Plan* g, const std::vector<int32_t>& bi, const std::vecto
   const bool dkeys = Q.algo == ALGO_RELIEFF;
   if (dkeys) g->ksplit = 1;
   g->kfull = g->ksplit > 1 ? 0 : g->n_tiles;  // k_dist can split only a tail; all or none here
-  g->alloc_target = 3;
+  DevArena& M = g->mem_shard;
   int rc = FS_OK;
   g->Dk = nullptr;
-  if ((rc = dkeys ? dalloc(g, (float**)&g->D_alloc, (size_t)g->dplane)
-                  : dalloc(g, (double**)&g->D_alloc, (size_t)g->dplane)) ||
+  if ((rc = dkeys ? M.alloc((float**)&g->D_alloc, (size_t)g->dplane)
+                  : M.alloc((double**)&g->D_alloc, (size_t)g->dplane)) ||
       (dkeys ? (g->Dk = (float*)g->D_alloc - (int64_t)g->win.x * Q.n_pad, g->D = nullptr)
              : (g->D = (double*)g->D_alloc - (g->tiled ? 0 : (int64_t)g->win.x * Q.n_pad)),
        false) ||
-      (rc = dalloc(g, &g->tiles, g->n_tiles)) ||
-      (rc = dalloc(g, &g->rspart, (size_t)std::max<int64_t>(g->n_tiles, 1) * 256))) {
+      (rc = M.alloc(&g->tiles, g->n_tiles)) ||
+      (rc = M.alloc(&g->rspart, (size_t)std::max<int64_t>(g->n_tiles, 1) * 256))) {
   } else if (Q.algo != ALGO_RELIEFF && !g->sparse) {
-    rc = dalloc(g, &g->Wt, (size_t)(g->n_tiles + 1) * kTile * kTile);
+    rc = M.alloc(&g->Wt, (size_t)(g->n_tiles + 1) * kTile * kTile);
   } else if (g->sparse) {
     // 64 KB per tile (k_weights_sparse3 writes every slot on every step)
     // and one spare tile: k_score_sparse3 prefetches the weights of a step
     // past the end of a stream (never used; zeroed once all the same).
     const size_t count = (size_t)(g->n_tiles + 1) * kTileWeights;
-    if (!(rc = dalloc(g, &g->wrow, count)) && !(rc = dalloc(g, &g->nnz, 1)) &&
+    if (!(rc = M.alloc(&g->wrow, count)) && !(rc = M.alloc(&g->nnz, 1)) &&
         hipMemsetAsync(g->wrow + (size_t)g->n_tiles * kTileWeights, 0,
                        sizeof(float) * kTileWeights, g->stream) != hipSuccess)
       rc = FS_EHIP;
   }
   if (!rc && g->ksplit > 1)
-    rc = dalloc(g, &g->Dpart,
+    rc = M.alloc(&g->Dpart,
                 (size_t)(g->n_tiles - g->kfull) * (g->ksplit - 1) * kTile * kTile);
-  g->alloc_target = 0;
   if (rc) return rc;
   g->nnz_valid = false;
   return h2d(g, g->tiles, tl.data(), g->n_tiles);
@@ -364,8 +336,7 @@ int plan_set_shard(Plan* g, int rank, int world) {
   FS_HIP(hipStreamSynchronize(g->stream));
   if (g->side) FS_HIP(hipStreamSynchronize(g->side));
   if (g->side2) FS_HIP(hipStreamSynchronize(g->side2));
-  for (void* q : g->owned_shard) dev_free(q);
-  g->owned_shard.clear();
+  g->mem_shard.release();
   g->D = g->Dpart = nullptr;
   g->D_alloc = nullptr;
   g->Wt = nullptr;
@@ -407,9 +378,8 @@ int plan_create(Plan** out, const Prepared& P, const void* x, int x_is_f64, int 
     return FS_EINVAL;
   }
   FS_HIP(hipSetDevice(device));
-  Plan* g = new Plan();
+  Plan* g = new Plan(device);
   g->P = P;
-  g->device = device;
   g->rank = rank;
   g->world = world;
   g->x_is_f64 = x_is_f64;
@@ -445,21 +415,24 @@ int plan_create(Plan** out, const Prepared& P, const void* x, int x_is_f64, int 
   }
   g->row_mode = row_mode;
   // (ReliefF refines in k_rf_select and uses only the counter)
-  g->list_cap = Q.algo == ALGO_RELIEFF ? 1 : std::max<int64_t>(1 << 16, Q.n * 64);
+  int64_t list_cap = Q.algo == ALGO_RELIEFF ? 1 : std::max<int64_t>(1 << 16, Q.n * 64);
+  if (test_hooks().list_cap >= 1) list_cap = test_hooks().list_cap;  // tests: reach its growth
   g->use_q16 = choose_q16(Q);
   const size_t xbytes = (size_t)Q.n * Q.p_in * (x_is_f64 ? 8 : 4);
+  DevArena& M = g->mem_plan;
   int rc;
   trace_mark("plan: host setup");
   // the library's staged copy of X (fs_stage_x, fs_stage_x_cast) is read in
   // place, else X is copied from a caller's staged copy or uploaded
   g->x_staged = staged_acquire(x, Q.n, Q.p_in, x_is_f64, g->device);
   if (g->x_staged) g->x = const_cast<void*>(g->x_staged);
-  if ((!g->x_staged && (rc = dalloc(g, (char**)&g->x, xbytes))) ||
-      (rc = dalloc(g, &g->lab, Q.n_pad)) ||
-      (rc = dalloc(g, &g->corr, Q.n_pad)) ||
-      (rc = dalloc(g, &g->corr_part, (int64_t)kRowcorrMaxSlices * Q.n_pad)) ||
-      (rc = dalloc(g, &g->thr, Q.n_pad)) ||
-      (rc = dalloc(g, &g->list, g->list_cap)) || (rc = dalloc(g, &g->list_count, 1)))
+  if ((!g->x_staged && (rc = M.alloc((char**)&g->x, xbytes))) ||
+      (rc = M.alloc(&g->lab, Q.n_pad)) ||
+      (rc = M.alloc(&g->corr, Q.n_pad)) ||
+      (rc = M.alloc(&g->corr_part, (int64_t)kRowcorrMaxSlices * Q.n_pad)) ||
+      (rc = M.alloc(&g->thr, Q.n_pad)) ||
+      (rc = g->list.reserve((size_t)list_cap, 0, &g->stream, 1)) ||
+      (rc = M.alloc(&g->list_count, 1)))
     return fail(rc);
   if (Q.algo == ALGO_MULTISURF) {
     // test hook: every row's threshold from exact distances (the machinery
@@ -467,7 +440,7 @@ int plan_create(Plan** out, const Prepared& P, const void* x, int x_is_f64, int 
     g->thr_all = test_hooks().thr_exact_all != 0;
     // thr_rows and uparts: size_exact_rows (plan_layout, per feature layout)
     g->thr_rows = (int)(g->thr_all ? Q.n : exact_thr_rows(Q.n, Q.pc + Q.pd));
-    if ((rc = dalloc(g, &g->unc, Q.n_pad)) || (rc = dalloc(g, &g->urows, Q.n_pad + 1)))
+    if ((rc = M.alloc(&g->unc, Q.n_pad)) || (rc = M.alloc(&g->urows, Q.n_pad + 1)))
       return fail(rc);
     // reference-order accumulation: exact_thresholds' batch counts (every
     // flagged row is fixed, in batches of thr_rows).  thr_rows changes with
@@ -476,13 +449,12 @@ int plan_create(Plan** out, const Prepared& P, const void* x, int x_is_f64, int 
     // later fs_plan_set_features may choose.  The decision masks
     // (n_pad^2 / 2 bytes) are allocated on first use by the one-device pass 2
     // (ref_masks): a multi-rank job writes into its own all-reduced buffer.
-    if (Q.ref_accum &&
-        (rc = dalloc(g, &g->bcnt, (size_t)(Q.n / kExactThrRows + 2))))
+    if (Q.ref_accum && (rc = M.alloc(&g->bcnt, (size_t)(Q.n / kExactThrRows + 2))))
       return fail(rc);
   }
   g->star_split = choose_star_split(Q, device);
   g->sparse = choose_sparse(g, Q);
-  if (g->star_split && (rc = dalloc(g, &g->alpha, Q.n_pad))) return fail(rc);
+  if (g->star_split && (rc = M.alloc(&g->alpha, Q.n_pad))) return fail(rc);
   if (g->star_split && Q.algo == ALGO_MULTISURF && !(g->side2 = stream_get(device)))
     return fail(FS_EHIP);
   if ((rc = setup_shard(g, bi, bj))) return fail(rc);
@@ -503,7 +475,7 @@ int plan_create(Plan** out, const Prepared& P, const void* x, int x_is_f64, int 
   if (Q.algo == ALGO_RELIEFF) {
     std::vector<uint8_t> lab8((size_t)Q.n_pad + 16, 0);
     for (int64_t j = 0; j < Q.n; j++) lab8[j] = (uint8_t)Q.labels[j];
-    if ((rc = dalloc(g, &g->lab8, lab8.size())) || (rc = h2d(g, g->lab8, lab8.data(), lab8.size())))
+    if ((rc = M.alloc(&g->lab8, lab8.size())) || (rc = h2d(g, g->lab8, lab8.data(), lab8.size())))
       return fail(rc);
   }
   if ((rc = plan_layout(g))) return fail(rc);
@@ -621,9 +593,9 @@ static int run_multisurf_shards(Plan* g, int shards, int rank, int world, double
     return plan_pass2(g, cnt, sc);
   }
   double *rs_v = nullptr, *cnt_v = nullptr, *sc_v = nullptr;
-  FS_TRY(dalloc(g, &rs_v, 3 * Q.n));
-  FS_TRY(dalloc(g, &cnt_v, 2 * Q.n));
-  FS_TRY(dalloc(g, &sc_v, Q.n_kept));
+  FS_TRY(g->mem_plan.alloc(&rs_v, 3 * Q.n));
+  FS_TRY(g->mem_plan.alloc(&cnt_v, 2 * Q.n));
+  FS_TRY(g->mem_plan.alloc(&sc_v, Q.n_kept));
   const int W = world * shards;
   auto add = [&](double* dst, const double* src, int64_t count, bool first) -> int {
     if (first)
@@ -764,7 +736,7 @@ int plan_decision_guard(Plan* g, const double* rowstats, const double* counts,
   // (max |score| of a partial sum would inflate the risk)
   if (g->r_lo != 0 || g->r_hi != Q.n) return FS_OK;
   FS_HIP(hipSetDevice(g->device));
-  if (!g->risk_dev) FS_TRY(dalloc(g, &g->risk_dev, 1));  // owned: lives as long as the plan
+  if (!g->risk_dev) FS_TRY(g->mem_plan.alloc(&g->risk_dev, 1));  // lives as long as the plan
   q16_decision_risk<<<1, 256, 0, g->stream>>>(rowstats, counts, sums, Q.n, Q.n_kept,
                                               (double)Q.pc, (double)(Q.pc + Q.pd), Q.SC,
                                               g->risk_dev);
@@ -800,8 +772,9 @@ int multisurf_run(const Prepared& P, const void* x, int device, float* scores_ou
   double *rs = nullptr, *cnt = nullptr, *sc = nullptr;
   int rc, switched = 0;
   double risk = -1.0;
-  if ((rc = dalloc(g, &rs, 3 * P.n)) || (rc = dalloc(g, &cnt, 2 * P.n)) ||
-      (rc = dalloc(g, &sc, P.n_kept)) || (rc = run_multisurf_shards(g, shards, 0, 1, rs, cnt, sc)) ||
+  if ((rc = g->mem_plan.alloc(&rs, 3 * P.n)) || (rc = g->mem_plan.alloc(&cnt, 2 * P.n)) ||
+      (rc = g->mem_plan.alloc(&sc, P.n_kept)) ||
+      (rc = run_multisurf_shards(g, shards, 0, 1, rs, cnt, sc)) ||
       (rc = plan_decision_guard(g, rs, cnt, sc, &risk, &switched)) ||
       (switched && (rc = run_multisurf_shards(g, shards, 0, 1, rs, cnt, sc))) ||
       (rc = finish_scores(g, sc, scores_out))) {
@@ -828,8 +801,8 @@ int multisurf_rows(const Prepared& P, const void* x, int device, int64_t r_lo, i
   FS_TRY(plan_create(&g, P, x, 0, device, 0, shards, 0));
   double *rs = nullptr, *cnt = nullptr, *sc = nullptr;
   int rc;
-  if ((rc = plan_set_rows(g, r_lo, r_hi)) || (rc = dalloc(g, &rs, 3 * P.n)) ||
-      (rc = dalloc(g, &cnt, 2 * P.n)) || (rc = dalloc(g, &sc, P.n_kept)) ||
+  if ((rc = plan_set_rows(g, r_lo, r_hi)) || (rc = g->mem_plan.alloc(&rs, 3 * P.n)) ||
+      (rc = g->mem_plan.alloc(&cnt, 2 * P.n)) || (rc = g->mem_plan.alloc(&sc, P.n_kept)) ||
       (rc = run_multisurf_shards(g, shards, 0, 1, rs, cnt, sc)) ||
       (rc = copy_sums(g, sc, sums_out))) {
     plan_destroy(g);
@@ -923,7 +896,7 @@ int surf_run_one(const Prepared& P, const void* x, int device, int64_t r_lo, int
   Plan* g = nullptr;
   FS_TRY(plan_create(&g, P, x, 1, device, 0, 1, 0, r_lo, r_hi));
   double* sc = nullptr;
-  int rc = dalloc(g, &sc, g->P.n_kept);
+  int rc = g->mem_plan.alloc(&sc, g->P.n_kept);
   if (rc == FS_OK && seed) {
     // reference order, a later row panel: the float32 column sums go on from
     // the previous panels' (SURF.py:195 is one sequential sum)
@@ -965,8 +938,7 @@ int plan_score(Plan* g, double* sums_dev) {
     return FS_EINVAL;
   }
   if (hipStreamSynchronize(g->stream) != hipSuccess && rc == FS_OK) rc = FS_EHIP;
-  for (void* q : g->scratch) dev_free(q);
-  g->scratch.clear();
+  g->mem_call.release();
   return rc;
 }
 

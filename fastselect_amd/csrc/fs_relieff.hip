@@ -1522,11 +1522,10 @@ static int relieff_select(Plan* g, const int64_t* dcc, int32_t* nbr, int32_t* nf
   if (nr_own <= 0) return FS_OK;
   uint32_t* tkey = nullptr;
   int32_t *tneed = nullptr, *teq = nullptr;
-  g->alloc_target = 2;  // per-call temporaries
-  FS_TRY(dalloc(g, &tkey, (size_t)n * C));
-  FS_TRY(dalloc(g, &tneed, (size_t)n * C));
-  FS_TRY(dalloc(g, &teq, (size_t)n * C));
-  g->alloc_target = 0;
+  DevArena& M = g->mem_call;  // per-call temporaries
+  FS_TRY(M.alloc(&tkey, (size_t)n * C));
+  FS_TRY(M.alloc(&tneed, (size_t)n * C));
+  FS_TRY(M.alloc(&teq, (size_t)n * C));
   // histograms: 1024 bins per class for n_classes <= 8 (10-bit first digit);
   // staged rows: 4 B of key + 1 B of class code per sample (by quads), for
   // n <= 32768 (one round trip of 8 quads per thread)
@@ -1620,12 +1619,10 @@ static int relieff_select(Plan* g, const int64_t* dcc, int32_t* nbr, int32_t* nf
   int32_t *drows = nullptr, *R = nullptr;
   float* keys = nullptr;
   int* status = nullptr;
-  g->alloc_target = 2;
-  FS_TRY(dalloc(g, &drows, (size_t)batch));
-  FS_TRY(dalloc(g, &R, (size_t)batch * n));
-  if (need_keys) FS_TRY(dalloc(g, &keys, (size_t)batch * n));
-  FS_TRY(dalloc(g, &status, 1));
-  g->alloc_target = 0;
+  FS_TRY(M.alloc(&drows, (size_t)batch));
+  FS_TRY(M.alloc(&R, (size_t)batch * n));
+  if (need_keys) FS_TRY(M.alloc(&keys, (size_t)batch * n));
+  FS_TRY(M.alloc(&status, 1));
   FS_HIP(hipMemsetAsync(status, 0, sizeof(int), g->stream));
   if (mw)
     FS_HIP(hipFuncSetAttribute((const void*)k_rf_ties_mw,
@@ -1695,18 +1692,13 @@ static int relieff_ref_ties(Plan* g, int32_t* nbr, const int32_t* nfound, const 
     if (trace_on()) std::fprintf(stderr, "[fs_trace] relieff reference order: no tied keys\n");
     return FS_OK;
   }
-  int rc;
   if (!test_hooks().rf_ref_replay) {
     // the replay reads the row's n keys (n * n_kept diffs); first drop the
     // rows whose sums come out the same in any order (k_rf_ref_order_matters,
     // C * k * n_kept diffs) -- on continuous data, all of them
     int32_t *crows = nullptr, *matters = nullptr;
-    g->alloc_target = 2;
-    if ((rc = dalloc(g, &crows, n_tied)) || (rc = dalloc(g, &matters, n_tied))) {
-      g->alloc_target = 0;
-      return rc;
-    }
-    g->alloc_target = 0;
+    FS_TRY(g->mem_call.alloc(&crows, n_tied));
+    FS_TRY(g->mem_call.alloc(&matters, n_tied));
     FS_TRY(h2d(g, crows, tie_rows.data(), n_tied));
     FS_TRY(refacc::relieff_order_matters(g->xk, g->Kp, g->krecip, g->kdisc, Q.n_kept, crows,
                                          (int64_t)n_tied, dup, nbr, nfound, g->r_lo, C, k,
@@ -1731,14 +1723,12 @@ static int relieff_ref_ties(Plan* g, int32_t* nbr, const int32_t* nfound, const 
   int32_t *drows = nullptr, *R = nullptr, *ord = nullptr;
   float* keys = nullptr;
   int* status = nullptr;
-  g->alloc_target = 2;
-  if ((rc = dalloc(g, &drows, (size_t)batch)) || (rc = dalloc(g, &R, (size_t)(batch * n))) ||
-      (rc = dalloc(g, &keys, (size_t)(batch * n))) ||
-      (rc = dalloc(g, &ord, (size_t)(batch * C * k))) || (rc = dalloc(g, &status, 1))) {
-    g->alloc_target = 0;
-    return rc;
-  }
-  g->alloc_target = 0;
+  DevArena& M = g->mem_call;
+  FS_TRY(M.alloc(&drows, (size_t)batch));
+  FS_TRY(M.alloc(&R, (size_t)(batch * n)));
+  FS_TRY(M.alloc(&keys, (size_t)(batch * n)));
+  FS_TRY(M.alloc(&ord, (size_t)(batch * C * k)));
+  FS_TRY(M.alloc(&status, 1));
   FS_HIP(hipMemsetAsync(status, 0, sizeof(int), g->stream));
   // keys and R in LDS (8 B per sample) beside ~2.2 KB of static LDS
   const bool in_lds = 8 * n + 2304 <= 160 * 1024;
@@ -1752,10 +1742,10 @@ static int relieff_ref_ties(Plan* g, int32_t* nbr, const int32_t* nfound, const 
                                     keys, g->stream));
     if (in_lds)
       k_rf_ref_ties<true><<<(unsigned)nr, 64, (size_t)(8 * n), g->stream>>>(
-          drows, n, keys, C, k, g->r_lo, nbr, nfound, g->rkeys, R, ord, status);
+          drows, n, keys, C, k, g->r_lo, nbr, nfound, g->rkeys.p, R, ord, status);
     else
       k_rf_ref_ties<false><<<(unsigned)nr, 64, 0, g->stream>>>(drows, n, keys, C, k, g->r_lo, nbr,
-                                                              nfound, g->rkeys, R, ord, status);
+                                                              nfound, g->rkeys.p, R, ord, status);
     FS_TRY(launch_check("k_rf_ref_ties"));
   }
   int hstatus = 0;
@@ -1782,15 +1772,12 @@ int plan_score_relieff(Plan* g, double* sums_dev) {
   int32_t *nbr = nullptr, *nfound = nullptr;
   const int64_t nrb = std::max<int64_t>(1, (g->r_hi - g->r_lo + kRfRows - 1) / kRfRows);
   int rc;
-  g->alloc_target = 2;  // per-call buffers
-  rc = dalloc(g, &dprior, C);
-  if (rc == FS_OK) rc = dalloc(g, &part, (size_t)nrb * Q.PW);
-  if (rc == FS_OK) rc = dalloc(g, &dcc, C);
-  if (rc == FS_OK) rc = dalloc(g, &nbr, (size_t)Q.n * C * std::max<int64_t>(k, 1));
-  if (rc == FS_OK) rc = dalloc(g, &nfound, (size_t)Q.n * C);
-  g->alloc_target = 0;
-  if (rc || (rc = h2d(g, dcc, cc.data(), C)) || (rc = h2d(g, dprior, prior.data(), C)) ||
-      (rc = run_quantize_dist(g)))
+  DevArena& M = g->mem_call;  // per-call buffers
+  if ((rc = M.alloc(&dprior, C)) || (rc = M.alloc(&part, (size_t)nrb * Q.PW)) ||
+      (rc = M.alloc(&dcc, C)) ||
+      (rc = M.alloc(&nbr, (size_t)Q.n * C * std::max<int64_t>(k, 1))) ||
+      (rc = M.alloc(&nfound, (size_t)Q.n * C)) || (rc = h2d(g, dcc, cc.data(), C)) ||
+      (rc = h2d(g, dprior, prior.data(), C)) || (rc = run_quantize_dist(g)))
     return rc;
   FS_HIP(hipEventRecord(g->ev[2], g->stream));
   if ((rc = relieff_select(g, dcc, nbr, nfound))) return rc;
@@ -1805,24 +1792,13 @@ int plan_score_relieff(Plan* g, double* sums_dev) {
     // from the previous row panel's sums when seeded (relieff_run)
     const int64_t rows = g->r_hi - g->r_lo;
     const size_t nkeys = (size_t)std::max<int64_t>(rows * C * std::max<int64_t>(k, 1), 1);
-    if (nkeys > g->rkeys_cap) {
-      if (g->rkeys) dev_free(g->rkeys);
-      g->rkeys = nullptr;
-      g->rkeys_cap = 0;
-      void* p = nullptr;
-      FS_TRY(dev_alloc(&p, nkeys * sizeof(float), g->device));
-      g->rkeys = (float*)p;
-      g->rkeys_cap = nkeys;
-    }
+    FS_TRY(g->rkeys.reserve(nkeys, 0, &g->stream, 1));
     float* temp = nullptr;
     FS_TRY(ref_temp(g, rows, &temp));
     int32_t* dup = nullptr;
-    g->alloc_target = 2;
-    rc = dalloc(g, &dup, (size_t)std::max<int64_t>(rows * C, 1));
-    g->alloc_target = 0;
-    FS_TRY(rc);
+    FS_TRY(M.alloc(&dup, (size_t)std::max<int64_t>(rows * C, 1)));
     FS_TRY(refacc::relieff_order(g->xk, g->Kp, g->krecip, g->kdisc, Q.n_kept, C, k, nbr, nfound,
-                                 g->r_lo, g->r_hi, g->rkeys, dup, g->stream));
+                                 g->r_lo, g->r_hi, g->rkeys.p, dup, g->stream));
     if (rows > 0 && k > 1 && Q.pc > 0) FS_TRY(relieff_ref_ties(g, nbr, nfound, dup));
     FS_TRY(refacc::relieff_update(g->xk, g->Kp, g->krecip, g->kdisc, g->lab, dprior, C, k, nbr,
                                   nfound, g->r_lo, g->r_hi, temp, g->stream));
@@ -1853,7 +1829,7 @@ int relieff_run_one(const Prepared& P, const void* x, int device, int64_t r_lo, 
   Plan* g = nullptr;
   FS_TRY(plan_create(&g, P, x, 0, device, 0, 1, 0, r_lo, r_hi));
   double* sc = nullptr;
-  int rc = dalloc(g, &sc, g->P.n_kept);
+  int rc = g->mem_plan.alloc(&sc, g->P.n_kept);
   if (rc == FS_OK && seed) {
     // reference order, a later row panel: the float32 column sums go on
     // from the previous panels' (ReliefF.py:219-220 is one sequential sum)

@@ -524,13 +524,8 @@ static int sort_pair_list(Plan* g, int64_t count) {
     set_error("pair list sort: temporary storage query failed");
     return FS_EHIP;
   }
-  if (need > g->sort_scratch_bytes) {
-    char* p = nullptr;
-    FS_TRY(dalloc(g, &p, need + need / 4));
-    g->sort_scratch = p;
-    g->sort_scratch_bytes = need + need / 4;
-  }
-  return sort_pairs(g->list, count, g->sort_scratch, g->sort_scratch_bytes, g->stream) == 0
+  FS_TRY(g->sort_scratch.reserve(need, need / 4, &g->stream, 1));
+  return sort_pairs(g->list.p, count, g->sort_scratch.p, g->sort_scratch.cap, g->stream) == 0
              ? FS_OK
              : FS_EHIP;
 }
@@ -545,18 +540,17 @@ static int refine_pairs(Plan* g, int algo, double delta, double thr_tol = 0.0,
   for (int attempt = 0; attempt < 2; attempt++) {
     FS_HIP(hipMemsetAsync(g->list_count, 0, sizeof(unsigned long long), g->stream));
     k_flag_pairs<<<(unsigned)g->n_tiles, 256, 0, g->stream>>>(
-        g->D, Q.n, Q.n_pad, g->tiled, g->win, g->tiles, g->thr, algo, 1.0 / Q.SC, delta, g->list,
-        g->list_cap, g->list_count);
+        g->D, Q.n, Q.n_pad, g->tiled, g->win, g->tiles, g->thr, algo, 1.0 / Q.SC, delta, g->list.p,
+        g->list.cap, g->list_count);
     FS_TRY(launch_check("k_flag_pairs"));
     unsigned long long cnt = 0;
     FS_HIP(hipMemcpyAsync(&cnt, g->list_count, sizeof(cnt), hipMemcpyDeviceToHost, g->stream));
     FS_HIP(hipStreamSynchronize(g->stream));
-    if ((int64_t)cnt <= g->list_cap) {
+    if (cnt <= g->list.cap) {
       g->n_refined = (int64_t)cnt;
       break;
     }
-    g->list_cap = (int64_t)cnt + cnt / 4;
-    FS_TRY(dalloc(g, &g->list, g->list_cap));
+    FS_TRY(g->list.reserve(cnt, cnt / 4, &g->stream, 1));
   }
   if (g->n_refined == 0) return FS_OK;
   FS_TRY(sort_pair_list(g, g->n_refined));
@@ -572,28 +566,28 @@ static int refine_pairs(Plan* g, int algo, double delta, double thr_tol = 0.0,
     const int64_t per_wg = FS_EXWG / 64;
     const unsigned rgrid = (unsigned)std::max<int64_t>(
         1, std::min<int64_t>((g->n_refined + per_wg - 1) / per_wg, FS_EXGRID));
-    if (ch4 < p4 && g->n_refined > g->pair_part_cap) {
-      g->pair_part_cap = std::max<int64_t>(g->n_refined, g->list_cap);
-      FS_TRY(dalloc(g, &g->pair_part, g->pair_part_cap));
+    if (ch4 < p4) {  // grown to the list's capacity (n_refined <= list.cap)
+      const size_t nr = (size_t)g->n_refined;
+      FS_TRY(g->pair_part.reserve(nr, g->list.cap - nr, &g->stream, 1));
     }
     for (int64_t c4 = 0; c4 < p4; c4 += ch4) {
       const int64_t hi4 = std::min(p4, c4 + ch4);
       k_exact_pairs_rows<<<rgrid, FS_EXWG, 0, g->stream>>>(
-          (const float*)g->x, Q.p_in, g->scl32, Q.SC, g->list, g->list_count, g->list_cap, c4,
-          hi4, c4 == 0, hi4 == p4, g->pair_part, Q.n_pad, g->tw, g->win, g->D, g->thr, thr_tol,
+          (const float*)g->x, Q.p_in, g->scl32, Q.SC, g->list.p, g->list_count, g->list.cap, c4,
+          hi4, c4 == 0, hi4 == p4, g->pair_part.p, Q.n_pad, g->tw, g->win, g->D, g->thr, thr_tol,
           unc);
       FS_TRY(launch_check("k_exact_pairs_rows"));
     }
     return FS_OK;
   } else if (g->x_is_f64)
     k_exact_pairs<double><<<grid, 256, 0, g->stream>>>(
-        (const double*)g->x, Q.p_in, Q.pc, Q.PC, Q.pd, g->src_col, g->scl, Q.SC, g->list,
-        g->list_count, g->list_cap, Q.n_pad, g->tw, g->win, 0, g->D, nullptr, g->thr, thr_tol,
+        (const double*)g->x, Q.p_in, Q.pc, Q.PC, Q.pd, g->src_col, g->scl, Q.SC, g->list.p,
+        g->list_count, g->list.cap, Q.n_pad, g->tw, g->win, 0, g->D, nullptr, g->thr, thr_tol,
         unc);
   else
     k_exact_pairs<float><<<grid, 256, 0, g->stream>>>(
-        (const float*)g->x, Q.p_in, Q.pc, Q.PC, Q.pd, g->src_col, g->scl, Q.SC, g->list,
-        g->list_count, g->list_cap, Q.n_pad, g->tw, g->win, 0, g->D, nullptr, g->thr, thr_tol,
+        (const float*)g->x, Q.p_in, Q.pc, Q.PC, Q.pd, g->src_col, g->scl, Q.SC, g->list.p,
+        g->list_count, g->list.cap, Q.n_pad, g->tw, g->win, 0, g->D, nullptr, g->thr, thr_tol,
         unc);
   return launch_check("k_exact_pairs");
 }
@@ -628,9 +622,9 @@ static int exact_thresholds_all(Plan* g) {
     const int32_t* rows = g->urows + (int64_t)b * B;
     k_row_exact_parts<float><<<dim3((unsigned)nchunk, ngroups), 256, 0, g->stream>>>(
         (const float*)g->x, Q.n, Q.p_in, Q.pc, Q.PC, Q.pd, g->src_col, g->scl, rows, g->bcnt + b,
-        B, g->uparts);
+        B, g->uparts.p);
     FS_TRY(launch_check("k_row_exact_parts"));
-    k_row_exact_thr<<<(unsigned)B, 64, 0, g->stream>>>(g->uparts, nchunk, rows, g->bcnt + b, B,
+    k_row_exact_thr<<<(unsigned)B, 64, 0, g->stream>>>(g->uparts.p, nchunk, rows, g->bcnt + b, B,
                                                         Q.n, Q.SC, g->thr);
     FS_TRY(launch_check("k_row_exact_thr"));
   }
@@ -662,13 +656,13 @@ static int exact_thresholds(Plan* g) {
   if (g->x_is_f64)
     k_row_exact_parts<double><<<dim3((unsigned)nchunk, ngroups), 256, 0, g->stream>>>(
         (const double*)g->x, Q.n, Q.p_in, Q.pc, Q.PC, Q.pd, g->src_col, g->scl, g->urows, nrows,
-        g->thr_rows, g->uparts);
+        g->thr_rows, g->uparts.p);
   else
     k_row_exact_parts<float><<<dim3((unsigned)nchunk, ngroups), 256, 0, g->stream>>>(
         (const float*)g->x, Q.n, Q.p_in, Q.pc, Q.PC, Q.pd, g->src_col, g->scl, g->urows, nrows,
-        g->thr_rows, g->uparts);
+        g->thr_rows, g->uparts.p);
   FS_TRY(launch_check("k_row_exact_parts"));
-  k_row_exact_thr<<<(unsigned)g->thr_rows, 64, 0, g->stream>>>(g->uparts, nchunk, g->urows, nrows,
+  k_row_exact_thr<<<(unsigned)g->thr_rows, 64, 0, g->stream>>>(g->uparts.p, nchunk, g->urows, nrows,
                                                                g->thr_rows, Q.n, Q.SC, g->thr);
   FS_TRY(launch_check("k_row_exact_thr"));
   if (trace_on()) {

@@ -277,7 +277,7 @@ static int exact_pairs(Plan* g, int64_t count) {
   const Prepared& Q = g->P;
   if (count <= 0) return FS_OK;
   k_surf_exact_pairs<<<(unsigned)count, 256, 0, g->stream>>>(
-      (const double*)g->x, Q.p_in, Q.pc, Q.PC, Q.pd, g->src_col, g->scl, g->list, g->D, Q.n_pad,
+      (const double*)g->x, Q.p_in, Q.pc, Q.PC, Q.pd, g->src_col, g->scl, g->list.p, g->D, Q.n_pad,
       g->win);
   return launch_check("k_surf_exact_pairs");
 }
@@ -288,18 +288,11 @@ int surf_resolve(Plan* g) {
   if (rows <= 0 || n < 2) return FS_OK;
   const double inv_sc = 1.0 / Q.SC, band = Q.amb_delta;
   int32_t *ra = nullptr, *rb = nullptr, *cnt = nullptr;
-  g->alloc_target = 2;
-  int rc;
-  if ((rc = dalloc(g, &ra, (size_t)rows)) || (rc = dalloc(g, &rb, (size_t)rows)) ||
-      (rc = dalloc(g, &cnt, 2))) {
-    g->alloc_target = 0;
-    return rc;
-  }
-  g->alloc_target = 0;
-  if (g->list_cap < kAvgPairsPerRound * rows) {  // the list lives with the plan
-    g->list_cap = kAvgPairsPerRound * rows;
-    FS_TRY(dalloc(g, &g->list, (size_t)g->list_cap));
-  }
+  FS_TRY(g->mem_call.alloc(&ra, (size_t)rows));
+  FS_TRY(g->mem_call.alloc(&rb, (size_t)rows));
+  FS_TRY(g->mem_call.alloc(&cnt, 2));
+  // (the list lives with the plan)
+  FS_TRY(g->list.reserve((size_t)(kAvgPairsPerRound * rows), 0, &g->stream, 1));
   {
     std::vector<int32_t> all((size_t)rows);
     for (int64_t r = 0; r < rows; r++) all[(size_t)r] = (int32_t)(g->r_lo + r);
@@ -311,7 +304,7 @@ int surf_resolve(Plan* g) {
   while (cur > 0) {
     FS_HIP(hipMemsetAsync(cnt, 0, 2 * sizeof(int32_t), g->stream));
     k_surf_avg_int<<<(unsigned)((cur + 63) / 64), 320, 0, g->stream>>>(
-        g->D, n, Q.n_pad, inv_sc, band, ra, cur, g->thr, rb, cnt, g->list);
+        g->D, n, Q.n_pad, inv_sc, band, ra, cur, g->thr, rb, cnt, g->list.p);
     FS_TRY(launch_check("k_surf_avg_int"));
     int32_t next[2] = {0, 0};
     FS_HIP(hipMemcpyAsync(next, cnt, sizeof(next), hipMemcpyDeviceToHost, g->stream));
@@ -331,16 +324,15 @@ int surf_resolve(Plan* g) {
     FS_HIP(hipMemsetAsync(g->list_count, 0, sizeof(unsigned long long), g->stream));
     const dim3 grid((unsigned)((n + 255) / 256), (unsigned)(g->win.y - g->win.x));
     k_surf_decisions<<<grid, 256, 0, g->stream>>>(g->D, n, Q.n_pad, g->win, inv_sc, band, g->thr,
-                                                  g->r_lo, g->r_hi, g->list, g->list_cap,
+                                                  g->r_lo, g->r_hi, g->list.p, g->list.cap,
                                                   g->list_count);
     FS_TRY(launch_check("k_surf_decisions"));
     unsigned long long c = 0;
     FS_HIP(hipMemcpyAsync(&c, g->list_count, sizeof(c), hipMemcpyDeviceToHost, g->stream));
     FS_HIP(hipStreamSynchronize(g->stream));
     ndec = (int64_t)c;
-    if (ndec <= g->list_cap) break;
-    g->list_cap = ndec + ndec / 4;
-    FS_TRY(dalloc(g, &g->list, (size_t)g->list_cap));
+    if ((size_t)ndec <= g->list.cap) break;
+    FS_TRY(g->list.reserve((size_t)ndec, (size_t)ndec / 4, &g->stream, 1));
   }
   FS_TRY(exact_pairs(g, ndec));
   const dim3 grid((unsigned)((n + 255) / 256), (unsigned)(g->win.y - g->win.x));
