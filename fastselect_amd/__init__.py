@@ -10,12 +10,14 @@ scikit-learn surface.  Scoring runs in hand-written HIP kernels for gfx950
 ``MDR`` is the reference's exhaustive k-way SNP interaction search, the usual
 second stage after a Relief filter; ``mRMR`` (with the
 ``fastselect_amd.mutual_information`` functions it is built on) drops
-redundant features in between.
+redundant features in between, and ``CFS`` picks a subset by correlation with
+the class against correlation within the subset.
 
 Importing the package loads the native library; it fails loudly if the
 library has not been built.
 """
 from . import _lib, mutual_information
+from .CFS import CFS
 from .MDR import MDR
 from .mRMR import mRMR
 from .MultiSURF import MultiSURF
@@ -29,12 +31,13 @@ from .TuRF import TuRF
 # attribute access cannot find them there and serialises the class by value:
 # dill does, and once a package that uses it (multiprocess, datasets) is
 # imported, so does joblib.dump.  Name the estimators by their public address.
-for _cls in (MultiSURF, ReliefF, SURF, TuRF, MDR, mRMR):
+for _cls in (MultiSURF, ReliefF, SURF, TuRF, MDR, mRMR, CFS):
     _cls.__module__ = __name__
 del _cls
 
 __version__ = "0.1.0"
-__all__ = ["ReliefF", "SURF", "MultiSURF", "SURFstar", "MultiSURFstar", "TuRF", "MDR", "mRMR"]
+__all__ = ["ReliefF", "SURF", "MultiSURF", "SURFstar", "MultiSURFstar", "TuRF", "MDR", "mRMR",
+           "CFS"]
 
 
 def gpu_available() -> bool:

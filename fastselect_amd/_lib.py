@@ -51,6 +51,8 @@ EXPORTED = (
     "fs_multisurf_score_ex", "fs_relieff_score_ex", "fs_surf_score_ex",
     "fs_mdr_scan", "fs_mdr_combinations", "fs_mdr_unrank",
     "fs_mi_matrices", "fs_mi_last_timing",
+    "fs_cfs_create", "fs_cfs_relevance", "fs_cfs_search", "fs_cfs_row", "fs_cfs_search_matrix",
+    "fs_cfs_last_timing", "fs_cfs_destroy",
 )
 
 
@@ -173,6 +175,18 @@ def _load() -> ctypes.CDLL:
     lib.fs_mi_matrices.restype = _int
     lib.fs_mi_last_timing.argtypes = [_f64p]
     lib.fs_mi_last_timing.restype = _int
+    lib.fs_cfs_create.argtypes = [ctypes.POINTER(_vp), _int, _int, _u8p, _u8p, _i64, _i64, _int,
+                                  _int]
+    lib.fs_cfs_relevance.argtypes = [_vp, _f32p]
+    lib.fs_cfs_search.argtypes = [_vp, ctypes.c_double, _i64p, _i64p, _f64p]
+    lib.fs_cfs_row.argtypes = [_vp, _i64, _f32p]
+    lib.fs_cfs_search_matrix.argtypes = [_int, _int, _f32p, _f32p, _i64, ctypes.c_double, _i64p,
+                                         _i64p, _f64p]
+    lib.fs_cfs_last_timing.argtypes = [_f64p]
+    lib.fs_cfs_destroy.argtypes = [_vp]
+    for name in ("fs_cfs_create", "fs_cfs_relevance", "fs_cfs_search", "fs_cfs_row",
+                 "fs_cfs_search_matrix", "fs_cfs_last_timing", "fs_cfs_destroy"):
+        getattr(lib, name).restype = _int
     for name in ("fs_column_stats", "fs_multisurf_score", "fs_multisurf_score_rows",
                  "fs_plan_set_rows", "fs_relieff_score", "fs_surf_score",
                  "fs_relieff_score_rows", "fs_surf_score_rows", "fs_plan_create",
@@ -809,4 +823,92 @@ def mi_last_timing():
     ``mi_matrices`` (``fs_mi_last_timing``; -1 where unavailable)."""
     v = np.full(4, -1.0)
     check(_lib.fs_mi_last_timing(_p(v, _f64p)))
+    return tuple(float(t) for t in v)
+
+
+class Cfs:
+    """A CFS handle (``fs_cfs_*``): the packed state codes of one fit, its
+    class correlations, and rows of symmetrical uncertainty computed when the
+    search selects their feature (replaces ``_precompute_correlations_cpu`` /
+    ``_gpu_kernel`` and ``_best_first_search``, CFS.py:80-162, 219-243).
+
+    ``codes`` (n x p) and ``ycodes`` (n) hold values in ``0..n_states-1``
+    (uint8)."""
+
+    def __init__(self, backend, codes, ycodes, n_states, n_jobs=-1, device=0):
+        self._h = _vp()
+        x = np.ascontiguousarray(codes, dtype=np.uint8)
+        if x.ndim != 2:
+            raise ValueError("codes must be a 2-D array")
+        self.n, self.p = x.shape
+        yv = np.ascontiguousarray(ycodes, dtype=np.uint8)
+        if yv.shape != (self.n,):
+            raise ValueError("ycodes must have one entry per row of codes")
+        check(_lib.fs_cfs_create(ctypes.byref(self._h), _backend_code(backend), int(device),
+                                 _p(x, _u8p), _p(yv, _u8p), self.n, self.p, int(n_states),
+                                 int(n_jobs)))
+
+    def relevance(self):
+        """float32 [p]: SU(X_f, y) (``fs_cfs_relevance``)."""
+        r = np.zeros(self.p, dtype=np.float32)
+        check(_lib.fs_cfs_relevance(self._h, _p(r, _f32p)))
+        return r
+
+    def search(self, min_r_cf=0.1):
+        """(selected int64 [k] in selection order, merits float64 [k]) of the
+        best-first search (``fs_cfs_search``)."""
+        sel = np.zeros(self.p, dtype=np.int64)
+        mer = np.zeros(self.p, dtype=np.float64)
+        k = _i64(0)
+        check(_lib.fs_cfs_search(self._h, float(min_r_cf), _p(sel, _i64p), ctypes.byref(k),
+                                 _p(mer, _f64p)))
+        return sel[:k.value].copy(), mer[:k.value].copy()
+
+    def row(self, feature):
+        """float32 [p]: SU(feature, .) with the diagonal 0 (``fs_cfs_row``)."""
+        r = np.zeros(self.p, dtype=np.float32)
+        check(_lib.fs_cfs_row(self._h, int(feature), _p(r, _f32p)))
+        return r
+
+    def close(self) -> None:
+        if self._h:
+            _lib.fs_cfs_destroy(self._h)
+            self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cfs_search_matrix(backend, r_cf, r_ff, min_r_cf=0.1, device=0):
+    """The best-first search of CFS on a caller's float32 ``r_cf`` [p] and
+    symmetric ``r_ff`` [p, p] (``fs_cfs_search_matrix``; ``_best_first_search``,
+    CFS.py:115-162).  Returns (selected int64 [k], merits float64 [k])."""
+    rc_ = np.ascontiguousarray(r_cf, dtype=np.float32)
+    rf = np.ascontiguousarray(r_ff, dtype=np.float32)
+    p = rc_.shape[0]
+    if rc_.ndim != 1 or rf.shape != (p, p):
+        raise ValueError("r_cf must be a vector of p entries and r_ff p x p")
+    sel = np.zeros(max(p, 1), dtype=np.int64)
+    mer = np.zeros(max(p, 1), dtype=np.float64)
+    k = _i64(0)
+    check(_lib.fs_cfs_search_matrix(_backend_code(backend), int(device), _p(rc_, _f32p),
+                                    _p(rf, _f32p), p, float(min_r_cf), _p(sel, _i64p),
+                                    ctypes.byref(k), _p(mer, _f64p)))
+    return sel[:k.value].copy(), mer[:k.value].copy()
+
+
+def cfs_last_timing():
+    """(upload, pack, relevance, rows, steps) milliseconds of this thread's
+    last GPU ``Cfs`` handle (``fs_cfs_last_timing``; -1 where unavailable)."""
+    v = np.full(5, -1.0)
+    check(_lib.fs_cfs_last_timing(_p(v, _f64p)))
     return tuple(float(t) for t in v)

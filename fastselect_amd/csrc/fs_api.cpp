@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/fastselect_amd.h"
+#include "fs_cfs.h"
 #include "fs_internal.h"
 #include "fs_mdr.h"
 #include "fs_mi.h"
@@ -155,6 +156,7 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "colsort_global") h.colsort_global = value;
   else if (k == "mi_tiles") h.mi_tiles = value;
   else if (k == "list_cap") h.list_cap = value;
+  else if (k == "cfs_rows_cap") h.cfs_rows_cap = value;
   else {
     set_error("fs_test_hook: unknown hook '" + k + "'");
     return FS_EINVAL;
@@ -1074,6 +1076,79 @@ int fs_mi_last_timing(double* ms4) {
     return FS_EINVAL;
   }
   gpu::mi_last_timing(ms4);
+  return FS_OK;
+}
+
+int fs_cfs_create(fs_cfs** out, int backend, int device, const uint8_t* codes,
+                  const uint8_t* ycodes, int64_t n, int64_t p, int n_states, int n_jobs) {
+  if (backend != FS_BACKEND_CPU && backend != FS_BACKEND_GPU) {
+    set_error("backend must be FS_BACKEND_CPU or FS_BACKEND_GPU");
+    return FS_EINVAL;
+  }
+  // the argument checks come before the device check, as in fs_mi_matrices
+  int rc = cfs_check(backend, out, codes, ycodes, n, p, n_states);
+  if (rc != FS_OK) return rc;
+  *out = nullptr;
+  if ((rc = check_backend(backend, device)) != FS_OK) return rc;
+  if (backend == FS_BACKEND_GPU) return gpu::cfs_create(out, device, codes, ycodes, n, p, n_states);
+  return cpu::cfs_create(out, codes, ycodes, n, p, n_states, n_jobs);
+}
+
+int fs_cfs_relevance(fs_cfs* h, float* r_cf) {
+  if (!h || !r_cf) {
+    set_error("fs_cfs_relevance: NULL argument");
+    return FS_EINVAL;
+  }
+  return h->relevance(r_cf);
+}
+
+int fs_cfs_search(fs_cfs* h, double min_r_cf, int64_t* selected, int64_t* n_selected,
+                  double* merits) {
+  if (!h || !selected || !n_selected || !merits) {
+    set_error("fs_cfs_search: NULL argument");
+    return FS_EINVAL;
+  }
+  return h->search(min_r_cf, selected, n_selected, merits);
+}
+
+int fs_cfs_row(fs_cfs* h, int64_t feature, float* row) {
+  if (!h || !row) {
+    set_error("fs_cfs_row: NULL argument");
+    return FS_EINVAL;
+  }
+  if (feature < 0 || feature >= h->p) {
+    set_error("fs_cfs_row: feature must be in [0, p)");
+    return FS_EINVAL;
+  }
+  return h->row(feature, row);
+}
+
+int fs_cfs_search_matrix(int backend, int device, const float* r_cf, const float* r_ff, int64_t p,
+                         double min_r_cf, int64_t* selected, int64_t* n_selected,
+                         double* merits) {
+  if (backend != FS_BACKEND_CPU && backend != FS_BACKEND_GPU) {
+    set_error("backend must be FS_BACKEND_CPU or FS_BACKEND_GPU");
+    return FS_EINVAL;
+  }
+  int rc = cfs_check_matrix(r_cf, r_ff, p, selected, n_selected, merits);
+  if (rc != FS_OK) return rc;
+  if ((rc = check_backend(backend, device)) != FS_OK) return rc;
+  if (backend == FS_BACKEND_GPU)
+    return gpu::cfs_search_matrix(device, r_cf, r_ff, p, min_r_cf, selected, n_selected, merits);
+  return cpu::cfs_search_matrix(r_cf, r_ff, p, min_r_cf, -1, selected, n_selected, merits);
+}
+
+int fs_cfs_last_timing(double* ms5) {
+  if (!ms5) {
+    set_error("fs_cfs_last_timing: NULL output");
+    return FS_EINVAL;
+  }
+  gpu::cfs_last_timing(ms5);
+  return FS_OK;
+}
+
+int fs_cfs_destroy(fs_cfs* h) {
+  delete h;
   return FS_OK;
 }
 

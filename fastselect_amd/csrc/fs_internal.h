@@ -145,6 +145,7 @@ struct TestHooks {
   int64_t colsort_global = 0;  // 1: the large-n (device sort) route at every n
   int64_t mi_tiles = 0;        // >= 1: tiles per launch of the mutual-information scan (fs_mi.hip)
   int64_t list_cap = 0;        // >= 1: pairs the ambiguous-pair list holds at first (plan_create)
+  int64_t cfs_rows_cap = 0;    // >= 1: rows the CFS row cache holds at first (fs_cfs.hip)
 };
 TestHooks& test_hooks();
 

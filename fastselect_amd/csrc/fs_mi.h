@@ -13,6 +13,9 @@
 #include <cstdint>
 
 #include "fs_internal.h"
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
 
 namespace fs {
 
@@ -82,6 +85,15 @@ int mi_matrices(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t
 // Milliseconds of the calling thread's last GPU mi_matrices: upload, pack,
 // scan, download (HIP events on the call's stream).
 void mi_last_timing(double* ms4);
+#if defined(__HIPCC__)
+// Launches k_mi_pack (fs_mi.hip) on `s` for another unit (fs_cfs.hip): codes
+// x [n][p] and y (as column p) -> planes[(w * P1p + c) * SP + s] over
+// (n + 31) / 32 words, P1p >= p + 1 columns (the padding zero), SP = n_states
+// rounded up to 4; kcol[c] = max code + 1 (zeroed by the caller), *bad |= 1
+// for a code >= S.
+hipError_t mi_pack(const uint8_t* x, const uint8_t* y, int64_t n, int64_t p, int64_t P1p, int S,
+                   int SP, uint32_t* planes, int32_t* kcol, int* bad, hipStream_t s);
+#endif
 }
 
 }  // namespace fs

@@ -233,6 +233,20 @@ __global__ __launch_bounds__(kMiThreads) void k_mi_scan(const MiScanArgs a) {
 
 }  // namespace
 
+hipError_t mi_pack(const uint8_t* x, const uint8_t* y, int64_t n, int64_t p, int64_t P1p, int S,
+                   int SP, uint32_t* planes, int32_t* kcol, int* bad, hipStream_t s) {
+  // grid.y is limited to 65535: pack the words in slabs
+  const int64_t W = (n + 31) / 32;
+  const unsigned gx = (unsigned)((P1p + 255) / 256);
+  for (int64_t w0 = 0; w0 < W; w0 += 65535) {
+    const int64_t wn = std::min<int64_t>(65535, W - w0);
+    k_mi_pack<<<dim3(gx, (unsigned)wn), 256, 0, s>>>(x, y, n, p, P1p, S, SP, w0, planes, kcol,
+                                                     bad);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 void mi_last_timing(double* ms4) {
   for (int k = 0; k < 4; k++) ms4[k] = g_mi_ms[k];
 }
@@ -314,16 +328,8 @@ int mi_matrices(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t
     fail("hipMemset", e);
   mark(1);
 
-  if (rc == FS_OK) {
-    // grid.y is limited to 65535: pack the words in slabs
-    const unsigned gx = (unsigned)((P1p + 255) / 256);
-    for (int64_t w0 = 0; w0 < W && rc == FS_OK; w0 += 65535) {
-      const int64_t wn = std::min<int64_t>(65535, W - w0);
-      k_mi_pack<<<dim3(gx, (unsigned)wn), 256, 0, s>>>(dx, dy, n, p, P1p, S, SP, w0, dplanes,
-                                                       dkcol, dbad);
-      if ((e = hipGetLastError()) != hipSuccess) fail("pack kernel", e);
-    }
-  }
+  if (rc == FS_OK && (e = mi_pack(dx, dy, n, p, P1p, S, SP, dplanes, dkcol, dbad, s)) != hipSuccess)
+    fail("pack kernel", e);
   mark(2);
   int bad = 0;
   if (rc == FS_OK && ((e = hipMemcpyAsync(&bad, dbad, 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||

@@ -584,6 +584,67 @@ FS_API int fs_mi_matrices(int backend, int device, const uint8_t* codes, const u
  * benchmark tool. */
 FS_API int fs_mi_last_timing(double* ms4);
 
+/* ---- CFS: correlation-based feature selection ----------------------------- */
+
+/*
+ * Symmetrical uncertainty SU(x, y) = 2 I(x; y) / (H(x) + H(y)) of integer-coded
+ * columns, float64 in the written order of _entropy, _mutual_information and
+ * _symmetrical_uncertainty (CFS.py:26-77, compiled numba's typing), stored as
+ * float32; the column with the lower index supplies a pair's table rows
+ * (CFS.py:96-102), the target counts as column p.  The handle keeps the packed
+ * state bit-planes and computes a row SU(f, .) when the search selects f: the
+ * p x p matrix of _precompute_correlations_{cpu, gpu_kernel} (CFS.py:80-104,
+ * 219-243) never exists.  The backends differ only through the host's and the
+ * device's log2().
+ */
+typedef struct fs_cfs fs_cfs;
+/*
+ * Uploads and packs the codes once and computes r_cf (replaces the r_cf half
+ * of _precompute_correlations_cpu, CFS.py:88-92).
+ *   codes    [n][p] row-major state codes, 0..n_states-1
+ *   ycodes   [n] codes of the target, same range
+ *   n_jobs   CPU threads (-1 = all); ignored by the GPU backend
+ * FS_EINVAL: NULL out / codes / ycodes, n < 1 or n >= 2^31, p < 1, n_states
+ * outside 1..256, a code >= n_states, more than 32 states on the GPU backend
+ * (CFS.py:349).  FS_EOOM when the planes do not fit (decided before any array
+ * is read).
+ */
+FS_API int fs_cfs_create(fs_cfs** out, int backend, int device, const uint8_t* codes,
+                         const uint8_t* ycodes, int64_t n, int64_t p, int n_states, int n_jobs);
+/* r_cf[p]: SU(X_f, y), the feature supplying the rows (CFS.py:88-92). */
+FS_API int fs_cfs_relevance(fs_cfs* h, float* r_cf);
+/*
+ * _best_first_search (CFS.py:115-162) on lazy rows: starts at argmax(r_cf)
+ * (empty when that is < min_r_cf), scans the unselected features with
+ * r_cf >= min_r_cf, sums in float64 in the reference's order, takes the
+ * lowest-index candidate of the highest merit while the merit grows.
+ *   selected    [p] capacity, in selection order
+ *   n_selected  the number selected
+ *   merits      [p] capacity: merits[s] = the merit after s + 1 features
+ */
+FS_API int fs_cfs_search(fs_cfs* h, double min_r_cf, int64_t* selected, int64_t* n_selected,
+                         double* merits);
+/*
+ * row[p] = SU(feature, .), the diagonal 0: one row of the reference's
+ * r_ff_matrix (CFS.py:94-102), from the handle's row cache if the last search
+ * selected the feature, else computed on the spot (same bits either way).
+ */
+FS_API int fs_cfs_row(fs_cfs* h, int64_t feature, float* row);
+/*
+ * _best_first_search (CFS.py:115-162) on a caller's r_cf[p] and symmetric
+ * r_ff[p][p] through the same step code as fs_cfs_search (r_ff[i, s] is read
+ * as row s, column i).
+ */
+FS_API int fs_cfs_search_matrix(int backend, int device, const float* r_cf, const float* r_ff,
+                                int64_t p, double min_r_cf, int64_t* selected,
+                                int64_t* n_selected, double* merits);
+/* Milliseconds the calling thread's last GPU handle spent on upload, pack,
+ * relevance, rows and steps (HIP events; the last two grow with every
+ * fs_cfs_search / fs_cfs_row; -1 where unavailable), for the benchmark tool. */
+FS_API int fs_cfs_last_timing(double* ms5);
+/* Frees the handle (NULL: nothing). */
+FS_API int fs_cfs_destroy(fs_cfs* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,258 @@
+"""CFS on the CPU backend (fs_cfs_cpu.cpp, CFS.py) against the numpy
+restatement in cfs_np.py.
+
+* Symmetrical uncertainty: every SU of fs_cfs_row over all features and of
+  fs_cfs_relevance equals the restatement's float32 or is the adjacent
+  float32: the two sides run the same IEEE operations in the same order
+  except log2 (numpy's against libm's), so a float64 difference near 1e-16
+  can move the float32 rounding by one step at most; at most 1 % of a case's
+  values may differ at all.
+* The search: fs_cfs_search_matrix on random float32 matrices gives the
+  restatement's selection and its merits bit for bit (IEEE operations in the
+  same order on both sides), including matrices in multiples of 1/8, where
+  equal merits occur and the lowest index decides.
+* The estimator and the C ABI.
+"""
+import ctypes
+import pickle
+
+import numpy as np
+import pytest
+from sklearn.base import clone
+from sklearn.exceptions import NotFittedError
+
+import cfs_np
+import mi_np
+
+SU_CASES = dict(mi_np.SHAPES)
+SU_CASES["p1"] = lambda: mi_np.uniform(65, 1, 3, 31) + (3,)
+SU_CASES["p2"] = lambda: mi_np.uniform(65, 2, 3, 32) + (3,)
+
+
+def check_su(got, want, what):
+    steps = cfs_np.f32_steps(got, want)
+    assert steps.max(initial=0) <= 1, what
+    assert np.count_nonzero(steps) <= 0.01 * steps.size, what
+
+
+@pytest.mark.parametrize("name", sorted(SU_CASES))
+def test_su_equals_restatement(name):
+    from fastselect_amd import _lib
+    X, y, S, r_cf, r_ff = cfs_np.su_case(name, SU_CASES[name])
+    p = X.shape[1]
+    with _lib.Cfs("cpu", X, y, S) as h:
+        check_su(h.relevance(), r_cf, "r_cf")
+        rows = np.stack([h.row(f) for f in range(p)])
+    check_su(rows, r_ff, "r_ff")
+    assert np.array_equal(rows, rows.T) and not np.diag(rows).any()
+
+
+def test_two_constant_columns_give_zero():
+    from fastselect_amd import _lib
+    X, y, S, _, r_ff = cfs_np.su_case("mixed", SU_CASES["mixed"])
+    assert r_ff[0, 7] == 0.0  # both constant: hx + hy < 1e-12
+    with _lib.Cfs("cpu", X, y, S) as h:
+        assert h.row(0)[7] == 0.0 and h.row(7)[0] == 0.0
+
+
+MATRICES = [(1, 0, False), (2, 6, False), (20, 1, False), (64, 2, False), (65, 3, True),
+            (40, 4, True), (30, 5, True), (33, 7, False)]
+
+
+@pytest.mark.parametrize("p,seed,eighths", MATRICES)
+def test_search_matrix_equals_restatement(p, seed, eighths):
+    from fastselect_amd import _lib
+    r_cf, r_ff = cfs_np.random_matrix(p, seed, eighths)
+    sel, mer, _ = cfs_np.best_first(r_cf, r_ff)
+    got_sel, got_mer = _lib.cfs_search_matrix("cpu", r_cf, r_ff)
+    assert list(got_sel) == sel
+    assert np.array_equal(got_mer, np.array(mer, dtype=np.float64))
+
+
+def test_search_matrix_ties_take_the_lowest_index():
+    """Equal class correlations and no pairwise correlation: every candidate
+    of a step has the same merit."""
+    from fastselect_amd import _lib
+    r_cf = np.full(6, 0.5, dtype=np.float32)
+    r_ff = np.zeros((6, 6), dtype=np.float32)
+    sel, mer, _ = cfs_np.best_first(r_cf, r_ff)
+    got_sel, got_mer = _lib.cfs_search_matrix("cpu", r_cf, r_ff)
+    assert sel == [0, 1, 2, 3, 4, 5] and list(got_sel) == sel
+    assert np.array_equal(got_mer, np.array(mer))
+    # below the threshold nothing is selected
+    none, _ = _lib.cfs_search_matrix("cpu", np.full(4, 0.05, np.float32), np.zeros((4, 4)))
+    assert none.size == 0
+
+
+@pytest.mark.parametrize("key", cfs_np.PLANTED)
+def test_planted_selection(key):
+    from fastselect_amd import CFS, _lib
+    X, y, S, r_cf, r_ff, sel, mer, kept, merit = cfs_np.planted_case(key)
+    with _lib.Cfs("cpu", X, y, S) as h:
+        got_sel, got_mer = h.search()
+    assert list(got_sel) == sel
+    np.testing.assert_allclose(got_mer, mer, rtol=1e-6, atol=0)
+    est = CFS(backend="cpu").fit(X, y)
+    assert est.selected_indices_.tolist() == sorted(kept)
+    assert abs(est.merit_ - merit) <= 1e-6 * merit
+    assert est.effective_backend_ == "cpu"
+
+
+def reference_fixture():
+    """The reference's own fixture, regenerated from its seed: 200 samples;
+    column 0 follows y closely, column 1 repeats column 0, column 2 follows y
+    loosely, column 3 is noise and column 4 constant."""
+    rs = np.random.RandomState(42)
+    n = 200
+    y = rs.randint(0, 2, n)
+    f0 = y + rs.normal(0, 0.1, n)
+    f1 = f0 + rs.normal(0, 0.05, n)
+    f2 = y + rs.normal(0, 0.5, n)
+    f2[y == 0] -= 0.5
+    f3 = rs.rand(n) * 10
+    f4 = np.full(n, 5.0)
+    return np.vstack([f0, f1, f2, f3, f4]).T, y
+
+
+def test_reference_fixture_estimator():
+    from fastselect_amd import CFS
+    X, y = reference_fixture()
+    est = CFS(n_bins=10, backend="cpu").fit(X, y)
+    assert est.selected_indices_.tolist() == [0, 2]
+    assert est.merit_ > 0
+    assert est.support_mask_.tolist() == [True, False, True, False, False]
+    assert est.n_features_in_ == 5 and not hasattr(est, "feature_names_in_")
+    assert est.transform(X).shape == (200, 2)
+    assert np.array_equal(est.get_support(), est.support_mask_)
+    # the noise-only columns select nothing
+    none = CFS(backend="cpu").fit(X[:, 3:], y)
+    assert none.selected_indices_.size == 0 and none.merit_ == 0.0
+    assert none.transform(X[:, 3:]).shape == (200, 0)
+    # a single column
+    one = CFS(backend="cpu").fit(X[:, :1], y)
+    assert one.selected_indices_.tolist() == [0] and one.merit_ > 0
+    # threads do not change the answer
+    t1 = CFS(backend="cpu", n_jobs=1).fit(X, y)
+    assert t1.selected_indices_.tolist() == [0, 2] and t1.merit_ == est.merit_
+
+
+def test_estimator_pandas_clone_pickle():
+    pd = pytest.importorskip("pandas")
+    from fastselect_amd import CFS
+    X, y = reference_fixture()
+    df = pd.DataFrame(X, columns=[f"f{i}" for i in range(5)])
+    est = CFS(backend="cpu")
+    with pytest.raises(NotFittedError):
+        est.transform(df)
+    est.fit(df, y)
+    assert est.feature_names_in_.tolist() == ["f0", "f1", "f2", "f3", "f4"]
+    out = est.transform(df)
+    assert isinstance(out, pd.DataFrame) and out.columns.tolist() == ["f0", "f2"]
+    c = clone(est)
+    assert c.get_params() == est.get_params()
+    assert set(est.get_params()) == {"n_bins", "strategy", "backend", "n_jobs", "device",
+                                     "min_r_cf"}
+    back = pickle.loads(pickle.dumps(est))
+    assert back.selected_indices_.tolist() == [0, 2] and back.merit_ == est.merit_
+    assert type(back).__module__ == "fastselect_amd"
+
+
+def test_min_r_cf_parameter():
+    """``min_r_cf`` reaches the search: the reference's 0.1 by default, and a
+    lower value selects on data whose class correlations stay below 0.1
+    (mdr_np.planted: the largest is 0.028)."""
+    import mdr_np
+    from fastselect_amd import CFS
+    X, y = mdr_np.planted(160, 60, pair=(7, 41))
+    r_cf, r_ff = cfs_np.matrices(X, y, 3)
+    assert CFS(backend="cpu").fit(X, y).selected_indices_.size == 0
+    for thr in (0.02, 0.0):
+        sel, _, margins = cfs_np.best_first(r_cf, r_ff, thr)
+        kept, gap = cfs_np.prune(sel, r_cf, r_ff)
+        assert min(margins) >= cfs_np.MARGIN and gap >= cfs_np.MARGIN
+        est = CFS(backend="cpu", min_r_cf=thr).fit(X, y)
+        assert est.selected_indices_.tolist() == sorted(kept)
+        want = cfs_np.final_merit(kept, r_cf, r_ff)
+        assert abs(est.merit_ - want) <= 1e-6 * want
+    Xr, yr = reference_fixture()
+    assert CFS(backend="cpu", min_r_cf=0.1).fit(Xr, yr).selected_indices_.tolist() == [0, 2]
+    for bad in (-0.1, 1.5, float("nan")):
+        with pytest.raises(ValueError, match="min_r_cf"):
+            CFS(backend="cpu", min_r_cf=bad).fit(Xr, yr)
+
+
+def test_estimator_errors():
+    from fastselect_amd import CFS, _lib
+    from fastselect_amd.SURF import SURF_GPU_MISSING
+    X, y = reference_fixture()
+    with pytest.raises(ValueError, match="backend"):
+        CFS(backend="tpu").fit(X, y)
+    if _lib.device_count() == 0:
+        with pytest.raises(RuntimeError) as e:
+            CFS(backend="gpu").fit(X, y)
+        assert str(e.value) == SURF_GPU_MISSING
+    with pytest.raises(NotFittedError):
+        CFS().transform(X)
+    wide = np.tile(np.arange(300)[:, None], (1, 2))
+    with pytest.raises(ValueError, match="CPU backend supports up to 256 unique states/bins."):
+        CFS(backend="cpu").fit(wide, np.arange(300) % 2)
+
+
+# ---- the C ABI ---------------------------------------------------------------
+u8p = ctypes.POINTER(ctypes.c_uint8)
+f32p = ctypes.POINTER(ctypes.c_float)
+
+
+def _create(L, backend, x, y, n, p, S, out=True):
+    h = ctypes.c_void_p()
+    rc = L.lib().fs_cfs_create(ctypes.byref(h) if out else None, backend, 0,
+                               None if x is None else x.ctypes.data_as(u8p),
+                               None if y is None else y.ctypes.data_as(u8p), n, p, S, 1)
+    return rc, h
+
+
+def test_abi_invalid_arguments():
+    from fastselect_amd import _lib as L
+    x = np.zeros((10, 3), np.uint8)
+    y = np.zeros(10, np.uint8)
+    for backend in (L.BACKEND_CPU, L.BACKEND_GPU):
+        assert _create(L, backend, None, y, 10, 3, 3)[0] == L.FS_EINVAL
+        assert _create(L, backend, x, None, 10, 3, 3)[0] == L.FS_EINVAL
+        assert _create(L, backend, x, y, 10, 3, 3, out=False)[0] == L.FS_EINVAL
+        assert _create(L, backend, x, y, 10, 0, 3)[0] == L.FS_EINVAL
+        assert _create(L, backend, x, y, 0, 3, 3)[0] == L.FS_EINVAL
+        assert _create(L, backend, x, y, 10, 3, 0)[0] == L.FS_EINVAL
+    assert _create(L, L.BACKEND_GPU, x, y, 10, 3, 33)[0] == L.FS_EINVAL
+    assert b"32 states" in L.lib().fs_last_error()
+    assert _create(L, L.BACKEND_CPU, x, y, 10, 3, 257)[0] == L.FS_EINVAL
+    assert _create(L, 7, x, y, 10, 3, 3)[0] == L.FS_EINVAL
+    bad = x.copy()
+    bad[9, 2] = 3
+    rc, h = _create(L, L.BACKEND_CPU, bad, y, 10, 3, 3)
+    assert rc == L.FS_EINVAL and not h.value
+    assert b"n_states" in L.lib().fs_last_error()
+    assert L.lib().fs_cfs_destroy(None) == L.FS_OK
+    assert L.lib().fs_cfs_relevance(None, None) == L.FS_EINVAL
+    assert L.lib().fs_cfs_row(None, 0, None) == L.FS_EINVAL
+    assert L.lib().fs_cfs_search(None, 0.1, None, None, None) == L.FS_EINVAL
+    assert L.lib().fs_cfs_search_matrix(L.BACKEND_CPU, 0, None, None, 3, 0.1, None, None,
+                                        None) == L.FS_EINVAL
+    assert L.lib().fs_cfs_last_timing(None) == L.FS_EINVAL
+    rc, h = _create(L, L.BACKEND_CPU, x, y, 10, 3, 3)
+    assert rc == L.FS_OK
+    row = np.zeros(3, np.float32)
+    assert L.lib().fs_cfs_row(h, 3, row.ctypes.data_as(f32p)) == L.FS_EINVAL
+    assert L.lib().fs_cfs_row(h, -1, row.ctypes.data_as(f32p)) == L.FS_EINVAL
+    assert L.lib().fs_cfs_destroy(h) == L.FS_OK
+
+
+def test_rows_before_and_after_search_are_the_same_bits():
+    from fastselect_amd import _lib
+    X, y, S, _, _, sel, _, _, _ = cfs_np.planted_case(cfs_np.PLANTED[0])
+    with _lib.Cfs("cpu", X, y, S) as h:
+        before = np.stack([h.row(f) for f in range(X.shape[1])])
+        got, _ = h.search()
+        after = np.stack([h.row(f) for f in range(X.shape[1])])
+        again, _ = h.search()
+    assert list(got) == sel and list(again) == sel
+    assert np.array_equal(before.view(np.int32), after.view(np.int32))
