@@ -53,6 +53,7 @@ EXPORTED = (
     "fs_mi_matrices", "fs_mi_last_timing",
     "fs_cfs_create", "fs_cfs_relevance", "fs_cfs_search", "fs_cfs_row", "fs_cfs_search_matrix",
     "fs_cfs_last_timing", "fs_cfs_destroy",
+    "fs_mrmr_select", "fs_mrmr_search_matrix", "fs_mrmr_last_timing",
 )
 
 
@@ -186,6 +187,12 @@ def _load() -> ctypes.CDLL:
     lib.fs_cfs_destroy.argtypes = [_vp]
     for name in ("fs_cfs_create", "fs_cfs_relevance", "fs_cfs_search", "fs_cfs_row",
                  "fs_cfs_search_matrix", "fs_cfs_last_timing", "fs_cfs_destroy"):
+        getattr(lib, name).restype = _int
+    lib.fs_mrmr_select.argtypes = [_int, _int, _u8p, _u8p, _i64, _i64, _int, _int, _int, _i64, _int,
+                                   _f64p, _i64p, _f64p]
+    lib.fs_mrmr_search_matrix.argtypes = [_int, _int, _f64p, _f64p, _i64, _int, _i64, _i64p]
+    lib.fs_mrmr_last_timing.argtypes = [_f64p]
+    for name in ("fs_mrmr_select", "fs_mrmr_search_matrix", "fs_mrmr_last_timing"):
         getattr(lib, name).restype = _int
     for name in ("fs_column_stats", "fs_multisurf_score", "fs_multisurf_score_rows",
                  "fs_plan_set_rows", "fs_relieff_score", "fs_surf_score",
@@ -911,4 +918,65 @@ def cfs_last_timing():
     last GPU ``Cfs`` handle (``fs_cfs_last_timing``; -1 where unavailable)."""
     v = np.full(5, -1.0)
     check(_lib.fs_cfs_last_timing(_p(v, _f64p)))
+    return tuple(float(t) for t in v)
+
+
+MRMR_METHODS = {"MID": 0, "MIQ": 1}
+
+
+def mrmr_select(backend, codes, ycodes, n_states, k, method="MID", unit="bit", n_jobs=-1,
+                device=0, want_rows=True):
+    """mRMR's selection without the redundancy matrix (``fs_mrmr_select``;
+    mRMR.py:96-117): the relevance, then per step one pick and one row of
+    mutual information, k p pairs in all.
+
+    ``codes`` (n x p) and ``ycodes`` (n) hold values in ``0..n_states-1``
+    (uint8).  Returns (selected int64 [k] in selection order, relevance
+    float64 [p], rows float64 [k, p] with ``rows[s] = I(.; X_selected[s])``, or
+    None without ``want_rows``)."""
+    x = np.ascontiguousarray(codes, dtype=np.uint8)
+    if x.ndim != 2:
+        raise ValueError("codes must be a 2-D array")
+    n, p = x.shape
+    yv = np.ascontiguousarray(ycodes, dtype=np.uint8)
+    if yv.shape != (n,):
+        raise ValueError("ycodes must have one entry per row of codes")
+    if unit not in MI_UNITS:
+        raise ValueError("unit must be 'bit' or 'nat'")
+    if method not in MRMR_METHODS:
+        raise ValueError("method must be 'MID' or 'MIQ'")
+    k = int(k)
+    rel = np.zeros(p, dtype=np.float64)
+    sel = np.zeros(max(k, 1), dtype=np.int64)
+    rows = np.zeros((k, p), dtype=np.float64) if want_rows and 1 <= k <= p else None
+    check(_lib.fs_mrmr_select(_backend_code(backend), int(device), _p(x, _u8p), _p(yv, _u8p), n, p,
+                              int(n_states), MI_UNITS[unit], MRMR_METHODS[method], k, int(n_jobs),
+                              _p(rel, _f64p), _p(sel, _i64p),
+                              None if rows is None else _p(rows, _f64p)))
+    return sel[:k], rel, rows
+
+
+def mrmr_search_matrix(backend, relevance, redundancy, k, method="MID", device=0):
+    """The greedy loop of mRMR on a caller's float64 ``relevance`` [p] and
+    symmetric ``redundancy`` [p, p] (``fs_mrmr_search_matrix``; mRMR.py:96-117).
+    Returns selected int64 [k] in selection order."""
+    rel = np.ascontiguousarray(relevance, dtype=np.float64)
+    red = np.ascontiguousarray(redundancy, dtype=np.float64)
+    p = rel.shape[0]
+    if rel.ndim != 1 or red.shape != (p, p):
+        raise ValueError("relevance must be a vector of p entries and redundancy p x p")
+    if method not in MRMR_METHODS:
+        raise ValueError("method must be 'MID' or 'MIQ'")
+    k = int(k)
+    sel = np.zeros(max(k, 1), dtype=np.int64)
+    check(_lib.fs_mrmr_search_matrix(_backend_code(backend), int(device), _p(rel, _f64p),
+                                     _p(red, _f64p), p, MRMR_METHODS[method], k, _p(sel, _i64p)))
+    return sel[:k]
+
+
+def mrmr_last_timing():
+    """(upload, pack, relevance, rows, steps) milliseconds of this thread's
+    last GPU ``mrmr_select`` (``fs_mrmr_last_timing``; -1 where unavailable)."""
+    v = np.full(5, -1.0)
+    check(_lib.fs_mrmr_last_timing(_p(v, _f64p)))
     return tuple(float(t) for t in v)

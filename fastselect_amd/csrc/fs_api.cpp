@@ -11,6 +11,7 @@
 #include "fs_internal.h"
 #include "fs_mdr.h"
 #include "fs_mi.h"
+#include "fs_mrmr.h"
 
 #include <chrono>
 #include <cstdio>
@@ -1149,6 +1150,48 @@ int fs_cfs_last_timing(double* ms5) {
 
 int fs_cfs_destroy(fs_cfs* h) {
   delete h;
+  return FS_OK;
+}
+
+int fs_mrmr_select(int backend, int device, const uint8_t* codes, const uint8_t* ycodes, int64_t n,
+                   int64_t p, int n_states, int unit, int method, int64_t k, int n_jobs,
+                   double* relevance, int64_t* selected, double* rows) {
+  if (backend != FS_BACKEND_CPU && backend != FS_BACKEND_GPU) {
+    set_error("backend must be FS_BACKEND_CPU or FS_BACKEND_GPU");
+    return FS_EINVAL;
+  }
+  // the argument checks come before the device check, as in fs_mi_matrices
+  int rc = mrmr_check(backend, codes, ycodes, n, p, n_states, unit, method, k, relevance, selected);
+  if (rc != FS_OK) return rc;
+  if ((rc = check_backend(backend, device)) != FS_OK) return rc;
+  if (backend == FS_BACKEND_GPU)
+    return gpu::mrmr_select(device, codes, ycodes, n, p, n_states, unit, method, k, relevance,
+                            selected, rows);
+  return cpu::mrmr_select(codes, ycodes, n, p, n_states, unit, method, k, n_jobs, relevance,
+                          selected, rows);
+}
+
+int fs_mrmr_search_matrix(int backend, int device, const double* relevance,
+                          const double* redundancy, int64_t p, int method, int64_t k,
+                          int64_t* selected) {
+  if (backend != FS_BACKEND_CPU && backend != FS_BACKEND_GPU) {
+    set_error("backend must be FS_BACKEND_CPU or FS_BACKEND_GPU");
+    return FS_EINVAL;
+  }
+  int rc = mrmr_check_matrix(relevance, redundancy, p, method, k, selected);
+  if (rc != FS_OK) return rc;
+  if ((rc = check_backend(backend, device)) != FS_OK) return rc;
+  if (backend == FS_BACKEND_GPU)
+    return gpu::mrmr_search_matrix(device, relevance, redundancy, p, method, k, selected);
+  return cpu::mrmr_search_matrix(relevance, redundancy, p, method, k, selected);
+}
+
+int fs_mrmr_last_timing(double* ms5) {
+  if (!ms5) {
+    set_error("fs_mrmr_last_timing: NULL output");
+    return FS_EINVAL;
+  }
+  gpu::mrmr_last_timing(ms5);
   return FS_OK;
 }
 

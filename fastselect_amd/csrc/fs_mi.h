@@ -11,6 +11,7 @@
 #pragma once
 
 #include <cstdint>
+#include <vector>
 
 #include "fs_internal.h"
 #if defined(__HIPCC__)
@@ -75,6 +76,23 @@ int mi_check(int backend, const uint8_t* codes, const uint8_t* ycodes, int64_t n
              int n_states, int unit, const double* relevance);
 
 namespace cpu {
+// The columns of one CPU call, packed once (fs_mi_cpu.cpp): the codes
+// column-major with y as column p, each column's state count (max code + 1)
+// and, up to kPlaneStates states, one 64-bit plane per state.
+struct MiColumns {
+  int64_t n = 0, p = 0, W = 0;
+  int S = 0;
+  bool planes_route = false;
+  std::vector<uint8_t> colT;     // [p + 1][n]
+  std::vector<uint64_t> planes;  // [p + 1][S][W]
+  std::vector<int32_t> kcol;     // [p + 1]
+};
+// `who` opens the error messages.  FS_EOOM, or FS_EINVAL for a code >= n_states.
+int mi_columns(MiColumns& m, const char* who, const uint8_t* codes, const uint8_t* ycodes,
+               int64_t n, int64_t p, int n_states, int n_jobs);
+// The table of the pair (i, j) into tab[a * S + b], a < kcol[i] (the rows are
+// column i's states), b < kcol[j].
+void mi_pair_table(const MiColumns& m, int64_t i, int64_t j, int32_t* tab);
 int mi_matrices(const uint8_t* codes, const uint8_t* ycodes, int64_t n, int64_t p, int n_states,
                 int unit, int n_jobs, double* relevance, double* redundancy, int32_t* counts_out);
 }

@@ -1,7 +1,8 @@
 // fs_mi_cpu.cpp -- the argument checks of fs_mi_matrices (both backends) and
 // its CPU backend: every pair's contingency table from the column-major
 // codes, the pairs split over host threads.  It replaces _mi_pair_cpu and
-// _batch_mi_cpu (mutual_information.py:25-63).
+// _batch_mi_cpu (mutual_information.py:25-63).  The packing (mi_columns) and
+// one pair's table (mi_pair_table) also serve fs_mrmr_cpu.cpp.
 //
 // Two ways to a table, chosen by the state count (measured):
 // up to kPlaneStates states a column is one 64-bit plane per state and a cell
@@ -11,6 +12,7 @@
 #include <atomic>
 #include <cstring>
 #include <new>
+#include <string>
 #include <thread>
 
 #include "../../include/fastselect_amd.h"
@@ -88,21 +90,24 @@ FS_MI_POPCNT void table_planes_hw(const uint64_t* pi, const uint64_t* pj, int64_
 
 }  // namespace
 
-int mi_matrices(const uint8_t* codes, const uint8_t* ycodes, int64_t n, int64_t p, int n_states,
-                int unit, int n_jobs, double* relevance, double* redundancy,
-                int32_t* counts_out) {
+int mi_columns(MiColumns& m, const char* who, const uint8_t* codes, const uint8_t* ycodes,
+               int64_t n, int64_t p, int n_states, int n_jobs) {
   const int S = n_states;
   const int64_t P1 = p + 1;  // y is column p
-  const bool planes_route = S <= kPlaneStates;
-  const int64_t W = (n + 63) / 64;
-  std::vector<uint8_t> colT;      // [P1][n] codes, column-major
-  std::vector<uint64_t> planes;   // [P1][S][W]
-  std::vector<int32_t> kcol((size_t)P1, 1);
+  m.n = n, m.p = p, m.S = S;
+  m.planes_route = S <= kPlaneStates;
+  m.W = (n + 63) / 64;
+  const int64_t W = m.W;
+  const bool planes_route = m.planes_route;
+  std::vector<uint8_t>& colT = m.colT;
+  std::vector<uint64_t>& planes = m.planes;
+  std::vector<int32_t>& kcol = m.kcol;
   try {
+    kcol.assign((size_t)P1, 1);
     colT.resize((size_t)P1 * n);
     if (planes_route) planes.assign((size_t)P1 * S * W, 0);
   } catch (const std::bad_alloc&) {
-    set_error("fs_mi_matrices: out of host memory for the column codes");
+    set_error(std::string(who) + ": out of host memory for the column codes");
     return FS_EOOM;
   }
   const int nt_all = hardware_threads(n_jobs);
@@ -140,13 +145,36 @@ int mi_matrices(const uint8_t* codes, const uint8_t* ycodes, int64_t n, int64_t 
     for (auto& t : th) t.join();
   }
   if (bad.load()) {
-    set_error("fs_mi_matrices: a code is >= n_states");
+    set_error(std::string(who) + ": a code is >= n_states");
     return FS_EINVAL;
   }
+  return FS_OK;
+}
+
+void mi_pair_table(const MiColumns& m, int64_t i, int64_t j, int32_t* tab) {
+  static const auto tabfn = have_popcnt() ? table_planes_hw : table_planes_sw;
+  const int S = m.S, ki = m.kcol[i], kj = m.kcol[j];
+  if (m.planes_route) {
+    tabfn(&m.planes[(size_t)i * S * m.W], &m.planes[(size_t)j * S * m.W], m.W, S, ki, kj, tab);
+  } else {
+    for (int a = 0; a < ki; a++) std::memset(&tab[(size_t)a * S], 0, (size_t)kj * 4);
+    const uint8_t* ci = &m.colT[(size_t)i * m.n];
+    const uint8_t* cj = &m.colT[(size_t)j * m.n];
+    for (int64_t s = 0; s < m.n; s++) tab[(size_t)ci[s] * S + cj[s]]++;
+  }
+}
+
+int mi_matrices(const uint8_t* codes, const uint8_t* ycodes, int64_t n, int64_t p, int n_states,
+                int unit, int n_jobs, double* relevance, double* redundancy,
+                int32_t* counts_out) {
+  const int S = n_states;
+  MiColumns m;
+  if (int rc = mi_columns(m, "fs_mi_matrices", codes, ycodes, n, p, n_states, n_jobs)) return rc;
+  const std::vector<int32_t>& kcol = m.kcol;
+  const int nt_all = hardware_threads(n_jobs);
   if (redundancy) std::memset(redundancy, 0, (size_t)p * p * sizeof(double));
   if (counts_out) std::memset(counts_out, 0, (size_t)p * p * S * S * sizeof(int32_t));
 
-  const auto tabfn = have_popcnt() ? table_planes_hw : table_planes_sw;
   // one task per first column i: its pair with y, then with every j > i
   const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(nt_all, p));
   std::atomic<int64_t> next{0};
@@ -155,19 +183,12 @@ int mi_matrices(const uint8_t* codes, const uint8_t* ycodes, int64_t n, int64_t 
     std::vector<double> p2((size_t)S);
     for (int64_t i = next++; i < p; i = next++) {
       const int ki = kcol[i];
-      const uint8_t* ci = &colT[(size_t)i * n];
       // j = p (the target) first, then the columns after i
       const int64_t jend = (redundancy || counts_out) ? p : i + 1;
       for (int64_t jj = i; jj < jend; jj++) {
         const int64_t j = jj == i ? p : jj;
         const int kj = kcol[j];
-        if (planes_route) {
-          tabfn(&planes[(size_t)i * S * W], &planes[(size_t)j * S * W], W, S, ki, kj, tab.data());
-        } else {
-          for (int a = 0; a < ki; a++) std::memset(&tab[(size_t)a * S], 0, (size_t)kj * 4);
-          const uint8_t* cj = &colT[(size_t)j * n];
-          for (int64_t s = 0; s < n; s++) tab[(size_t)ci[s] * S + cj[s]]++;
-        }
+        mi_pair_table(m, i, j, tab.data());
         const double mi = mi_from_table(tab.data(), S, ki, kj, n, unit, p2.data());
         if (j == p) {
           relevance[i] = mi;

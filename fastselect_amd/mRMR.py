@@ -12,6 +12,14 @@ written (mRMR.py:102-134); the loop is O(k p).  It reads only the k selected
 columns of the redundancy matrix; the full matrix is computed because
 ``redundancy_matrix_`` is a fitted attribute of the reference.
 
+``redundancy="selected"`` is the path for callers who do not need that
+attribute: after the same validation and encoding, one call to
+``fs_mrmr_select`` computes the relevance and one row of mutual information per
+selected feature and runs the same greedy loop natively (on the GPU: every
+step queued on one stream, one synchronisation per fit).  That is k p pairs
+instead of p^2 / 2 and k p float64 of results instead of p^2, so a width whose
+matrix cannot be allocated (80 GB at p = 100000) still fits.
+
 With backend='gpu' the whole redundancy matrix is computed on the GPU (the
 reference computes it on the CPU whatever the backend,
 mutual_information.py:191-193).
@@ -43,27 +51,41 @@ class mRMR(TransformerMixin, BaseEstimator):
         CPU threads for backend='cpu' (-1 = all).  Not a reference parameter.
     device : int, default=0
         GPU ordinal for the GPU backend.  Not a reference parameter.
+    redundancy : {'matrix', 'selected'}, default='matrix'
+        Not a reference parameter.  'matrix' computes the whole p x p
+        redundancy matrix (p^2 / 2 pairs, 8 p^2 bytes on the device and the
+        host) and keeps it as ``redundancy_matrix_``, as the reference does.
+        'selected' computes only the rows of the selected features (k p pairs,
+        8 k p bytes), selects the same features from the same values, and sets
+        ``redundancy_rows_`` instead of ``redundancy_matrix_``.
 
     Attributes
     ----------
     relevance_scores_ : ndarray of float64, shape (n_features,)
     redundancy_matrix_ : ndarray of float64, shape (n_features, n_features)
+        With redundancy='matrix' only.
+    redundancy_rows_ : ndarray of float64, shape (n_features_to_select, n_features)
+        With redundancy='selected' only: ``redundancy_rows_[s]`` is row
+        ``top_features_[s]`` of the matrix.
     top_features_ : ndarray of int32, shape (n_features_to_select,)
     feature_importances_ : ndarray (the relevance scores)
     n_features_in_, unique_vals_, effective_backend_
     """
 
     def __init__(self, n_features_to_select: int, method: str = "MID", backend: str = "cpu",
-                 n_jobs: int = -1, device: int = 0):
+                 n_jobs: int = -1, device: int = 0, redundancy: str = "matrix"):
         self.n_features_to_select = n_features_to_select
         self.method = method
         self.backend = backend
         self.n_jobs = n_jobs
         self.device = device
+        self.redundancy = redundancy
         if self.method not in ["MID", "MIQ"]:
             raise ValueError("Method must be either 'MID' or 'MIQ'.")
         if self.backend not in ["cpu", "gpu", "auto"]:
             raise ValueError("Backend must be either 'cpu' or 'gpu' (or 'auto').")
+        if self.redundancy not in ["matrix", "selected"]:
+            raise ValueError("redundancy must be either 'matrix' or 'selected'.")
         if self.backend == "gpu" and not _lib.gpu_available():
             raise RuntimeError(_base.GPU_MISSING)
 
@@ -87,6 +109,8 @@ class mRMR(TransformerMixin, BaseEstimator):
         if backend == "auto" and unique_vals.size > mi._MAX_STATES_GPU:
             backend = "cpu"
         self.effective_backend_ = _base.effective_backend(backend)
+        if self.redundancy == "selected":
+            return self._fit_selected(X_encoded, y_encoded)
         relevance, redundancy = mi.calculate_mi_matrices(
             X_encoded, y_encoded, backend=self.effective_backend_, unit="bit",
             n_jobs=self.n_jobs, device=self.device)
@@ -117,6 +141,25 @@ class mRMR(TransformerMixin, BaseEstimator):
             redundancy_sum += self.redundancy_matrix_[:, best]
 
         self.top_features_ = selected_indices
+        self.feature_importances_ = self.relevance_scores_
+        return self
+
+    def _fit_selected(self, X_encoded, y_encoded):
+        """The relevance, the selection and the selected features' rows in one
+        ``fs_mrmr_select`` call, behind calculate_mi_matrices' own checks
+        (mutual_information.py:171-182)."""
+        if X_encoded.ndim != 2 or y_encoded.ndim != 1 or X_encoded.shape[0] != y_encoded.shape[0]:
+            raise ValueError("X must be 2‑D and y 1‑D with matching sample size")
+        X_d = mi._validate_discrete(X_encoded, "X")
+        y_d = mi._validate_discrete(y_encoded, "y")
+        max_state = int(max(X_d.max(), y_d.max())) + 1
+        where = mi._choose_backend(self.effective_backend_, max_state)
+        selected, relevance, rows = _lib.mrmr_select(
+            where, X_d, y_d, max_state, self.n_features_to_select, method=self.method,
+            unit="bit", n_jobs=self.n_jobs, device=self.device)
+        self.relevance_scores_ = relevance
+        self.redundancy_rows_ = rows
+        self.top_features_ = selected.astype(np.int32)
         self.feature_importances_ = self.relevance_scores_
         return self
 

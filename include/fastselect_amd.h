@@ -645,6 +645,48 @@ FS_API int fs_cfs_last_timing(double* ms5);
 /* Frees the handle (NULL: nothing). */
 FS_API int fs_cfs_destroy(fs_cfs* h);
 
+/* ---- mRMR: selection without the redundancy matrix ------------------------ */
+
+/*
+ * The greedy selection of mRMR.fit (mRMR.py:96-117) on rows of mutual
+ * information computed when their feature is selected: the relevance
+ * I(X_f; y), then per step the scores (MID: rel - rsum / i, MIQ: rel /
+ * (rsum / i + 1e-9), mRMR.py:104-107), the candidates within
+ * np.isclose(scores, max, atol=1e-12) (mRMR.py:109) resolved by the lowest
+ * mean redundancy and then the lowest index (mRMR.py:110-114), and
+ * rsum += I(.; X_best) (mRMR.py:117).  k p pairs instead of the p^2 / 2 of
+ * calculate_mi_matrices (mRMR.py:94-96); nothing of size p x p is allocated.
+ * Every value is the entry fs_mi_matrices computes on the same backend, bit
+ * for bit.  The GPU backend queues all k steps on one stream and synchronises
+ * once.
+ *   method      0 = MID, 1 = MIQ
+ *   relevance   [p]
+ *   selected    [k] in selection order
+ *   rows        NULL, or [k][p] float64 with rows[s][c] = I(X_c; X_selected[s]),
+ *               0.0 at c == selected[s]
+ *   n_jobs      CPU threads (-1 = all); ignored by the GPU backend
+ * codes, ycodes, n, p, n_states, unit: as fs_mi_matrices.  FS_EINVAL: as
+ * fs_mi_matrices, and k outside 1..p, method outside 0..1, NULL selected.
+ * FS_EOOM when the planes and rows do not fit (decided before any array is
+ * read).
+ */
+FS_API int fs_mrmr_select(int backend, int device, const uint8_t* codes, const uint8_t* ycodes,
+                          int64_t n, int64_t p, int n_states, int unit, int method, int64_t k,
+                          int n_jobs, double* relevance, int64_t* selected, double* rows);
+/*
+ * The same step code (mRMR.py:96-117) on a caller's relevance[p] and symmetric
+ * redundancy[p][p] (the picked feature's row is read): for tests that pin the
+ * tie rules, and for callers who hold a matrix already.
+ */
+FS_API int fs_mrmr_search_matrix(int backend, int device, const double* relevance,
+                                 const double* redundancy, int64_t p, int method, int64_t k,
+                                 int64_t* selected);
+/* Milliseconds the calling thread's last GPU fs_mrmr_select spent on upload,
+ * pack, relevance (with the first pick), rows and steps (HIP events; -1 where
+ * unavailable: above 64 steps the loop is timed as a whole, in `rows`), for
+ * the benchmark tool. */
+FS_API int fs_mrmr_last_timing(double* ms5);
+
 #ifdef __cplusplus
 }
 #endif
