@@ -301,6 +301,38 @@ hipStream_t stream_get(int device);
 void stream_put(int device, hipStream_t s);
 hipEvent_t event_get(int device, bool timing);
 void event_put(int device, hipEvent_t e, bool timing);
+// A pooled stream and timing events for one call or one handle.  Declare it
+// after the arenas and buffers whose blocks the stream uses: it is destroyed
+// first, so the stream is synchronised before any block is freed on every
+// return path.
+struct StreamLease {
+  int device;
+  hipStream_t s = nullptr;
+  std::vector<hipEvent_t> ev;
+  explicit StreamLease(int dev) : device(dev) {}
+  StreamLease(const StreamLease&) = delete;
+  StreamLease& operator=(const StreamLease&) = delete;
+  int open(size_t events) {  // stream_get / event_get have set the error
+    if (!(s = stream_get(device))) return FS_EHIP;
+    for (size_t k = 0; k < events; k++) {
+      ev.push_back(event_get(device, true));
+      if (!ev.back()) return FS_EHIP;
+    }
+    return FS_OK;
+  }
+  ~StreamLease() {
+    if (s) {
+      (void)hipStreamSynchronize(s);
+      stream_put(device, s);
+    }
+    for (hipEvent_t e : ev) event_put(device, e, true);
+    (void)hipGetLastError();
+  }
+};
+inline int no_device() {
+  set_error("backend='gpu' requested but no HIP device is visible");
+  return FS_ENODEV;
+}
 // fs_pass1.hip
 int choose_ksplit(int64_t tiles, int device, int nchunks, int64_t feats, bool beside);
 int calibrate_band(Plan* g);

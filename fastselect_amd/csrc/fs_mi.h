@@ -23,6 +23,7 @@ namespace fs {
 constexpr int kMiMaxStates = 256;      // codes are bytes
 constexpr int kMiMaxStatesGpu = 32;    // mutual_information.py:66 _MAX_STATES_GPU
 constexpr int64_t kMiMaxN = (int64_t)1 << 31;
+constexpr double kMiMaxBytes = 1e15;   // a larger device block is FS_EOOM before any allocation
 
 // _mi_pair_cpu's float64 expressions in their written order
 // (mutual_information.py:31-46) on an integer table tab[a * ld + b], a < k1
@@ -104,13 +105,33 @@ int mi_matrices(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t
 // scan, download (HIP events on the call's stream).
 void mi_last_timing(double* ms4);
 #if defined(__HIPCC__)
-// Launches k_mi_pack (fs_mi.hip) on `s` for another unit (fs_cfs.hip): codes
-// x [n][p] and y (as column p) -> planes[(w * P1p + c) * SP + s] over
-// (n + 31) / 32 words, P1p >= p + 1 columns (the padding zero), SP = n_states
-// rounded up to 4; kcol[c] = max code + 1 (zeroed by the caller), *bad |= 1
-// for a code >= S.
-hipError_t mi_pack(const uint8_t* x, const uint8_t* y, int64_t n, int64_t p, int64_t P1p, int S,
-                   int SP, uint32_t* planes, int32_t* kcol, int* bad, hipStream_t s);
+struct DevArena;
+// From codes to packed planes, for every unit that scans them (fs_mi.hip,
+// fs_cfs.hip, fs_mrmr.hip): codes x [n][p] and y (as column p) ->
+// planes[(w * P1p + c) * SP + s] over W = (n + 31) / 32 words, SP = n_states
+// rounded up to 4 (NB blocks of 4), P1p = p + 1 columns rounded up to a
+// multiple of `pad` (the padding zero); kcol[c] = max code + 1.  In call
+// order: shape, alloc, upload, pack (k_mi_pack), fetch_bad, and after a
+// synchronisation check.  The caller records its own events in between and
+// chooses where it synchronises.  `who` opens the error messages.
+struct MiPlanes {
+  const char* who = "";
+  int64_t n = 0, p = 0, P1 = 0, P1p = 0, W = 0;
+  int S = 0, NB = 0, SP = 0;
+  uint8_t *dx = nullptr, *dy = nullptr;  // the uploaded codes: dead after pack
+  uint32_t* planes = nullptr;
+  int32_t* kcol = nullptr;
+  int* dbad = nullptr;
+  int bad = 0;  // fetch_bad's target: a code is >= n_states
+  // The geometry, and FS_EOOM for sizes beyond any device.
+  int shape(const char* who_, int64_t n_, int64_t p_, int n_states, int pad);
+  // planes, kcol, dbad from `mem`, dx, dy from `up` (may be the same arena).
+  int alloc(DevArena& mem, DevArena& up);
+  int upload(const uint8_t* codes, const uint8_t* ycodes, hipStream_t s);
+  int pack(hipStream_t s);
+  int fetch_bad(hipStream_t s);
+  int check() const;  // FS_EINVAL for a code >= n_states
+};
 #endif
 }
 

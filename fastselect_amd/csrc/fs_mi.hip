@@ -13,32 +13,34 @@
 //               coalesced.  Also each column's state count (max code + 1, the
 //               reference's k1) and a flag for a code >= n_states.
 //   k_mi_scan   one workgroup per tile (column block I) x (column block J),
-//               I <= J, T columns each.  Per chunk of kMiWC words it stages
+//               I <= J, T columns each.  Per chunk of kPtWC words it stages
 //               both blocks' planes in LDS, [word][column][state], and every
 //               lane accumulates popcount(plane_i[a] & plane_j[b]) for ONE
-//               4 x 4 block of ONE pair's table in 16 registers, both operands
-//               from LDS with one 16-byte read each.  A pair takes NB^2 lanes
-//               (NB = SP / 4 blocks a side), so T = 16 / NB and T * SP <= 64:
-//               16 x 16 pairs at up to 4 states, 2 x 2 pairs at 32.  The
-//               epilogue runs in the same kernel on the same lanes: pxy into
-//               LDS (over the dead staging area), the marginals in index
-//               order, every cell's term on the lane that counted it, and the
-//               pair's first lane adds the terms row-major (fs_mi.h) and
-//               writes redundancy[i][j], [j][i] or relevance[i].  No table
-//               reaches HBM unless counts_out is asked for; no atomics touch
-//               a result.
+//               4 x 4 block of ONE pair's table in 16 registers (pt_count,
+//               fs_pairtab.h), both operands from LDS with one 16-byte read
+//               each.  A pair takes NB^2 lanes (NB = SP / 4 blocks a side), so
+//               T = 16 / NB and T * SP <= 64: 16 x 16 pairs at up to 4 states,
+//               2 x 2 pairs at 32.  The epilogue runs in the same kernel on
+//               the same lanes: pxy into LDS (over the dead staging area),
+//               the marginals in index order, every cell's term on the lane
+//               that counted it, and the pair's first lane adds the terms
+//               row-major (fs_mi.h) and writes redundancy[i][j], [j][i] or
+//               relevance[i].  These are the steps of pt_epilogue
+//               (fs_pairtab.h, which k_cfs_row and k_mi_row run) in a copy of
+//               this kernel's own, kept on a measurement: the note in the
+//               kernel.  No table reaches HBM unless counts_out is asked for;
+//               no atomics touch a result.
+// The host side of "codes to packed planes" (MiPlanes, fs_mi.h) is here too.
 #include "fs_gpu_internal.h"
 #include "fs_mi.h"
+#include "fs_pairtab.h"
 
 namespace fs {
 namespace gpu {
 
 namespace {
 
-constexpr int kMiThreads = 256;
-constexpr int kMiWC = 64;          // words (2048 samples) staged per chunk
 constexpr int kMiRow = 64;         // most words of one staged word row: T * SP
-constexpr int kMiMarg = 1024;      // most marginals of a tile: T * T * SP
 
 thread_local double g_mi_ms[4] = {-1.0, -1.0, -1.0, -1.0};
 
@@ -102,11 +104,11 @@ __device__ __forceinline__ void mi_tile(int64_t nb, int64_t t, int64_t& bi, int6
   bj = r + (t - tile_linear(nb, r, r));
 }
 
-__global__ __launch_bounds__(kMiThreads) void k_mi_scan(const MiScanArgs a) {
+__global__ __launch_bounds__(kPtThreads) void k_mi_scan(const MiScanArgs a) {
   // staging: [side][word][T * SP]; after the scan: the tile's pxy, then terms
-  __shared__ __align__(16) uint32_t s_raw[2 * kMiWC * kMiRow];
-  __shared__ double s_p1[kMiMarg];
-  __shared__ double s_p2[kMiMarg];
+  __shared__ __align__(16) uint32_t s_raw[2 * kPtWC * kMiRow];
+  __shared__ double s_p1[kPtMarg];
+  __shared__ double s_p2[kPtMarg];
   const int tid = threadIdx.x;
   const int SP = a.SP, NB = a.NB, T = a.T;
   const int NP = T * SP;       // words of one staged word row
@@ -119,12 +121,14 @@ __global__ __launch_bounds__(kMiThreads) void k_mi_scan(const MiScanArgs a) {
   } else {
     mi_tile(a.nbt, a.t0 + blockIdx.x, bi, bj);
   }
-  const int q = tid / L, blk = tid - q * L;
-  const int ab = blk / NB, bb = blk - ab * NB;
-  const int ii = q / T, jj = q - ii * T;
-  const bool lane_on = q < T * T;
+  PtLane g;
+  g.q = tid / L;
+  const int blk = tid - g.q * L;
+  g.ab = blk / NB, g.bb = blk - g.ab * NB;
+  const int ii = g.q / T, jj = g.q - ii * T;
+  g.lane_on = g.q < T * T;
   const int64_t i = bi * T + ii, j = bj * T + jj;
-  const bool pair_on = lane_on && i < j && j <= a.p && (!a.only_y || j == a.p);
+  g.pair_on = g.lane_on && i < j && j <= a.p && (!a.only_y || j == a.p);
 
   uint32_t c[16];
 #pragma unroll
@@ -134,66 +138,57 @@ __global__ __launch_bounds__(kMiThreads) void k_mi_scan(const MiScanArgs a) {
   const uint32_t* gi = a.planes + (size_t)bi * NP;
   const uint32_t* gj = a.planes + (size_t)bj * NP;
   uint4* si = reinterpret_cast<uint4*>(s_raw);
-  uint4* sj = reinterpret_cast<uint4*>(s_raw + kMiWC * kMiRow);
-  const int oi = (ii * SP + 4 * ab) / 4, oj = (jj * SP + 4 * bb) / 4;
-  for (int64_t w0 = 0; w0 < a.W; w0 += kMiWC) {
-    const int wn = a.W - w0 < kMiWC ? (int)(a.W - w0) : kMiWC;
-    for (int v = tid; v < wn * nv; v += kMiThreads) {
+  uint4* sj = reinterpret_cast<uint4*>(s_raw + kPtWC * kMiRow);
+  const int oi = (ii * SP + 4 * g.ab) / 4, oj = (jj * SP + 4 * g.bb) / 4;
+  for (int64_t w0 = 0; w0 < a.W; w0 += kPtWC) {
+    const int wn = a.W - w0 < kPtWC ? (int)(a.W - w0) : kPtWC;
+    for (int v = tid; v < wn * nv; v += kPtThreads) {
       const int w = v / nv, xq = v - w * nv;
-      const size_t g = (size_t)(w0 + w) * row + 4 * (size_t)xq;
-      si[v] = *reinterpret_cast<const uint4*>(gi + g);
-      sj[v] = *reinterpret_cast<const uint4*>(gj + g);
+      const size_t gw = (size_t)(w0 + w) * row + 4 * (size_t)xq;
+      si[v] = *reinterpret_cast<const uint4*>(gi + gw);
+      sj[v] = *reinterpret_cast<const uint4*>(gj + gw);
     }
     __syncthreads();
-    if (pair_on) {
-      for (int w = 0; w < wn; w++) {
-        const uint4 A = si[w * nv + oi], B = sj[w * nv + oj];
-        c[0] += __builtin_popcount(A.x & B.x);
-        c[1] += __builtin_popcount(A.x & B.y);
-        c[2] += __builtin_popcount(A.x & B.z);
-        c[3] += __builtin_popcount(A.x & B.w);
-        c[4] += __builtin_popcount(A.y & B.x);
-        c[5] += __builtin_popcount(A.y & B.y);
-        c[6] += __builtin_popcount(A.y & B.z);
-        c[7] += __builtin_popcount(A.y & B.w);
-        c[8] += __builtin_popcount(A.z & B.x);
-        c[9] += __builtin_popcount(A.z & B.y);
-        c[10] += __builtin_popcount(A.z & B.z);
-        c[11] += __builtin_popcount(A.z & B.w);
-        c[12] += __builtin_popcount(A.w & B.x);
-        c[13] += __builtin_popcount(A.w & B.y);
-        c[14] += __builtin_popcount(A.w & B.z);
-        c[15] += __builtin_popcount(A.w & B.w);
-      }
-    }
+    if (g.pair_on)
+      for (int w = 0; w < wn; w++) pt_count(si[w * nv + oi], sj[w * nv + oj], c);
     __syncthreads();
   }
 
-  if (a.counts && pair_on && j < a.p) {
+  if (a.counts && g.pair_on && j < a.p) {
     int32_t* out = a.counts + ((size_t)i * a.p + j) * a.S * a.S;
 #pragma unroll
     for (int r = 0; r < 4; r++)
 #pragma unroll
       for (int k = 0; k < 4; k++)
-        if (4 * ab + r < a.S && 4 * bb + k < a.S)
-          out[(size_t)(4 * ab + r) * a.S + 4 * bb + k] = (int32_t)c[r * 4 + k];
+        if (4 * g.ab + r < a.S && 4 * g.bb + k < a.S)
+          out[(size_t)(4 * g.ab + r) * a.S + 4 * g.bb + k] = (int32_t)c[r * 4 + k];
   }
 
-  // epilogue (fs_mi.h): pxy, marginals in index order, terms, row-major sum
+  // The epilogue: pt_epilogue's steps (fs_pairtab.h) without the transposition
+  // (i < j always), in this kernel's own copy.  Instantiating the shared
+  // function here gave the same instructions in another schedule and measured
+  // slower against the parent build on 2000 x 5000 x 3: the kernel 1907-1925 us
+  // against 1899-1900 us, the scan phase 1.96-1.98 ms against 1.93-1.97 ms, in
+  // four sessions; this copy measured 1888-1905 us and 1.93-1.95 ms
+  // (profiles/pairtab/README.md).  Whoever changes one of the two changes the
+  // other: tests/test_gpu_mrmr_selected.py asserts that k_mi_row's values equal
+  // this kernel's bit for bit.  The tile's pxy and terms go over the dead
+  // staging area.
   double* s_px = reinterpret_cast<double*>(s_raw);  // [pair][SP][SP], <= 4096 doubles
   const double dn = (double)a.n;
-  const int tb = q * SP * SP + 4 * ab * SP + 4 * bb;
+  const int q = g.q;
+  const int tb = q * SP * SP + 4 * g.ab * SP + 4 * g.bb;
   double px[16];
 #pragma unroll
   for (int k = 0; k < 16; k++) px[k] = mi_pxy((int32_t)c[k], dn);
-  if (lane_on) {
+  if (g.lane_on) {
 #pragma unroll
     for (int r = 0; r < 4; r++)
 #pragma unroll
       for (int k = 0; k < 4; k++) s_px[tb + r * SP + k] = px[r * 4 + k];
   }
   __syncthreads();
-  for (int it = tid; it < T * T * SP; it += kMiThreads) {
+  for (int it = tid; it < T * T * SP; it += kPtThreads) {
     const int q2 = it / SP, s = it - q2 * SP;
     const double* t = s_px + q2 * SP * SP;
     double r1 = 0.0, r2 = 0.0;
@@ -203,17 +198,18 @@ __global__ __launch_bounds__(kMiThreads) void k_mi_scan(const MiScanArgs a) {
     s_p2[it] = r2;
   }
   __syncthreads();
-  if (pair_on) {
+  if (g.pair_on) {
 #pragma unroll
     for (int r = 0; r < 4; r++)
 #pragma unroll
       for (int k = 0; k < 4; k++)
         s_px[tb + r * SP + k] =
-            mi_term(px[r * 4 + k], s_p1[q * SP + 4 * ab + r], s_p2[q * SP + 4 * bb + k]);
+            mi_term(px[r * 4 + k], s_p1[q * SP + 4 * g.ab + r], s_p2[q * SP + 4 * g.bb + k]);
   }
   __syncthreads();
-  if (pair_on && blk == 0) {
-    const int k1 = a.kcol[i], k2 = a.kcol[j];
+  if (g.pair_on && blk == 0) {
+    // the state counts bounded by SP, as in pt_epilogue
+    const int k1 = a.kcol[i] < SP ? a.kcol[i] : SP, k2 = a.kcol[j] < SP ? a.kcol[j] : SP;
     const double* t = s_px + q * SP * SP;
     double mi = 0.0;
     for (int r = 0; r < k1; r++)
@@ -233,18 +229,57 @@ __global__ __launch_bounds__(kMiThreads) void k_mi_scan(const MiScanArgs a) {
 
 }  // namespace
 
-hipError_t mi_pack(const uint8_t* x, const uint8_t* y, int64_t n, int64_t p, int64_t P1p, int S,
-                   int SP, uint32_t* planes, int32_t* kcol, int* bad, hipStream_t s) {
+int MiPlanes::shape(const char* who_, int64_t n_, int64_t p_, int n_states, int pad) {
+  who = who_, n = n_, p = p_, S = n_states;
+  NB = (S + 3) / 4, SP = NB * 4;
+  P1 = p + 1, P1p = (P1 + pad - 1) / pad * pad;
+  W = (n + 31) / 32;
+  // sizes in floating point first: a request beyond any device is an
+  // out-of-memory answer, not an overflowed size
+  if ((double)W * (double)P1p * SP * 4.0 > kMiMaxBytes || (double)n * (double)p > kMiMaxBytes) {
+    set_error(std::string(who) + ": the bit-planes do not fit the device memory");
+    return FS_EOOM;
+  }
+  return FS_OK;
+}
+
+int MiPlanes::alloc(DevArena& mem, DevArena& up) {
+  FS_TRY(up.alloc(&dx, (size_t)n * p));
+  FS_TRY(up.alloc(&dy, (size_t)n));
+  FS_TRY(mem.alloc(&planes, (size_t)W * P1p * SP));
+  FS_TRY(mem.alloc(&kcol, (size_t)P1));
+  return mem.alloc(&dbad, 1);
+}
+
+int MiPlanes::upload(const uint8_t* codes, const uint8_t* ycodes, hipStream_t s) {
+  FS_HIP(hipMemcpyAsync(dx, codes, (size_t)n * p, hipMemcpyHostToDevice, s));
+  FS_HIP(hipMemcpyAsync(dy, ycodes, (size_t)n, hipMemcpyHostToDevice, s));
+  FS_HIP(hipMemsetAsync(dbad, 0, 4, s));
+  FS_HIP(hipMemsetAsync(kcol, 0, (size_t)P1 * 4, s));  // k_mi_pack takes maxima
+  return FS_OK;
+}
+
+int MiPlanes::pack(hipStream_t s) {
   // grid.y is limited to 65535: pack the words in slabs
-  const int64_t W = (n + 31) / 32;
   const unsigned gx = (unsigned)((P1p + 255) / 256);
   for (int64_t w0 = 0; w0 < W; w0 += 65535) {
     const int64_t wn = std::min<int64_t>(65535, W - w0);
-    k_mi_pack<<<dim3(gx, (unsigned)wn), 256, 0, s>>>(x, y, n, p, P1p, S, SP, w0, planes, kcol,
-                                                     bad);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    k_mi_pack<<<dim3(gx, (unsigned)wn), 256, 0, s>>>(dx, dy, n, p, P1p, S, SP, w0, planes, kcol,
+                                                     dbad);
+    FS_TRY(launch_check("k_mi_pack"));
   }
-  return hipSuccess;
+  return FS_OK;
+}
+
+int MiPlanes::fetch_bad(hipStream_t s) {
+  FS_HIP(hipMemcpyAsync(&bad, dbad, 4, hipMemcpyDeviceToHost, s));
+  return FS_OK;
+}
+
+int MiPlanes::check() const {
+  if (!bad) return FS_OK;
+  set_error(std::string(who) + ": a code is >= n_states");
+  return FS_EINVAL;
 }
 
 void mi_last_timing(double* ms4) {
@@ -254,135 +289,75 @@ void mi_last_timing(double* ms4) {
 int mi_matrices(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t n, int64_t p,
                 int n_states, int unit, double* relevance, double* redundancy,
                 int32_t* counts_out) {
-  if (device_count() <= 0) {
-    set_error("backend='gpu' requested but no HIP device is visible");
-    return FS_ENODEV;
-  }
+  if (device_count() <= 0) return no_device();
   for (double& v : g_mi_ms) v = -1.0;
-  const int S = n_states;
-  const int NB = (S + 3) / 4, SP = NB * 4, T = 16 / NB;
-  const int64_t P1 = p + 1;
-  const int64_t nbt = (P1 + T - 1) / T, P1p = nbt * T;
-  const int64_t W = (n + 31) / 32;
-  // sizes in floating point first: a request beyond any device is an
-  // out-of-memory answer, not an overflowed size
-  const double kMaxBytes = 1e15;
-  const double red_bytes = redundancy ? (double)p * (double)p * 8.0 : 0.0;
-  const double cnt_bytes = counts_out ? (double)p * (double)p * (double)S * S * 4.0 : 0.0;
-  const double pl_bytes = (double)W * (double)P1p * SP * 4.0;
-  if (red_bytes > kMaxBytes || cnt_bytes > kMaxBytes || pl_bytes > kMaxBytes ||
-      (double)n * (double)p > kMaxBytes) {
+  MiPlanes pl;
+  const int T = 16 / ((n_states + 3) / 4);  // columns of a tile's side
+  FS_TRY(pl.shape("fs_mi_matrices", n, p, n_states, T));
+  const int S = pl.S;
+  if ((redundancy && (double)p * (double)p * 8.0 > kMiMaxBytes) ||
+      (counts_out && (double)p * (double)p * (double)S * S * 4.0 > kMiMaxBytes)) {
     set_error("fs_mi_matrices: the matrices do not fit the device memory");
     return FS_EOOM;
   }
   const size_t nred = redundancy ? (size_t)p * p : 0;
   const size_t ncnt = counts_out ? (size_t)p * p * S * S : 0;
-  const size_t plane_words = (size_t)W * P1p * SP;
 
-  uint8_t *dx = nullptr, *dy = nullptr;
-  uint32_t* dplanes = nullptr;
-  int32_t *dkcol = nullptr, *dcnt = nullptr;
+  FS_HIP(hipSetDevice(device));
+  DevArena mem(device);
+  StreamLease lease(device);  // destroyed (and the stream synchronised) before `mem`
+  FS_TRY(lease.open(5));
+  hipStream_t s = lease.s;
+  std::vector<hipEvent_t>& ev = lease.ev;
+  int32_t* dcnt = nullptr;
   double *dred = nullptr, *drel = nullptr;
-  int* dbad = nullptr;
-  hipStream_t s = nullptr;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  int rc = FS_OK;
-  auto fail = [&](const char* what, hipError_t e) {
-    set_error(std::string("fs_mi_matrices: ") + what + ": " + hipGetErrorString(e));
-    (void)hipGetLastError();
-    rc = (e == hipErrorOutOfMemory) ? FS_EOOM : FS_EHIP;
-  };
-  auto mark = [&](int k) {
-    hipError_t e;
-    if (rc == FS_OK && (e = hipEventRecord(ev[k], s)) != hipSuccess) fail("hipEventRecord", e);
-  };
-  hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess) fail("hipSetDevice", e);
-  if (rc == FS_OK && (e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess)
-    fail("hipStreamCreate", e);
-  for (int k = 0; k < 5 && rc == FS_OK; k++)
-    if ((e = hipEventCreate(&ev[k])) != hipSuccess) fail("hipEventCreate", e);
-  DevArena mem(device);  // freed on return, after the stream is synchronised
-  if (rc == FS_OK) rc = mem.alloc(&dx, (size_t)n * p);
-  if (rc == FS_OK) rc = mem.alloc(&dy, (size_t)n);
-  if (rc == FS_OK) rc = mem.alloc(&dplanes, plane_words);
-  if (rc == FS_OK) rc = mem.alloc(&dkcol, (size_t)P1);
-  if (rc == FS_OK) rc = mem.alloc(&drel, (size_t)p);
-  if (rc == FS_OK) rc = mem.alloc(&dbad, 1);
-  if (rc == FS_OK && nred) rc = mem.alloc(&dred, nred);
-  if (rc == FS_OK && ncnt) rc = mem.alloc(&dcnt, ncnt);
+  // every block is allocated before any array is read
+  FS_TRY(pl.alloc(mem, mem));
+  FS_TRY(mem.alloc(&drel, (size_t)p));
+  if (nred) FS_TRY(mem.alloc(&dred, nred));
+  if (ncnt) FS_TRY(mem.alloc(&dcnt, ncnt));
 
-  mark(0);
-  if (rc == FS_OK && ((e = hipMemcpyAsync(dx, codes, (size_t)n * p, hipMemcpyHostToDevice, s)) !=
-                          hipSuccess ||
-                      (e = hipMemcpyAsync(dy, ycodes, (size_t)n, hipMemcpyHostToDevice, s)) !=
-                          hipSuccess))
-    fail("upload of the codes", e);
-  if (rc == FS_OK && ((e = hipMemsetAsync(dbad, 0, 4, s)) != hipSuccess ||
-                      (e = hipMemsetAsync(dkcol, 0, (size_t)P1 * 4, s)) != hipSuccess))
-    fail("hipMemset", e);
+  FS_HIP(hipEventRecord(ev[0], s));
+  FS_TRY(pl.upload(codes, ycodes, s));
   // the diagonal, and every cell of counts_out that no pair writes, stay zero
-  if (rc == FS_OK && nred && (e = hipMemsetAsync(dred, 0, nred * 8, s)) != hipSuccess)
-    fail("hipMemset", e);
-  if (rc == FS_OK && ncnt && (e = hipMemsetAsync(dcnt, 0, ncnt * 4, s)) != hipSuccess)
-    fail("hipMemset", e);
-  mark(1);
+  if (nred) FS_HIP(hipMemsetAsync(dred, 0, nred * 8, s));
+  if (ncnt) FS_HIP(hipMemsetAsync(dcnt, 0, ncnt * 4, s));
+  FS_HIP(hipEventRecord(ev[1], s));
+  FS_TRY(pl.pack(s));
+  FS_HIP(hipEventRecord(ev[2], s));
+  FS_TRY(pl.fetch_bad(s));
+  FS_HIP(hipStreamSynchronize(s));
+  FS_TRY(pl.check());
 
-  if (rc == FS_OK && (e = mi_pack(dx, dy, n, p, P1p, S, SP, dplanes, dkcol, dbad, s)) != hipSuccess)
-    fail("pack kernel", e);
-  mark(2);
-  int bad = 0;
-  if (rc == FS_OK && ((e = hipMemcpyAsync(&bad, dbad, 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-                      (e = hipStreamSynchronize(s)) != hipSuccess))
-    fail("pack", e);
-  if (rc == FS_OK && bad) {
-    set_error("fs_mi_matrices: a code is >= n_states");
-    rc = FS_EINVAL;
+  // launches of about 2e11 lane operations each (a few milliseconds at the
+  // VALU peak), so that no launch holds the device for long: per tile and
+  // word 256 lanes run 16 ANDs and 16 popcount-accumulates
+  MiScanArgs a;
+  a.planes = pl.planes, a.kcol = pl.kcol, a.n = n, a.p = p, a.P1p = pl.P1p, a.W = pl.W;
+  a.S = S, a.SP = pl.SP, a.NB = pl.NB, a.T = T, a.nbt = pl.P1p / T, a.unit = unit;
+  a.only_y = nred == 0 && ncnt == 0;
+  a.red = dred, a.rel = drel, a.counts = dcnt;
+  const int64_t tiles = a.only_y ? a.nbt : a.nbt * (a.nbt + 1) / 2;
+  const double ops = 256.0 * 32.0 * (double)pl.W;
+  int64_t per = (int64_t)std::max(1024.0, std::min(2e11 / ops, 1e9));
+  if (test_hooks().mi_tiles > 0) per = test_hooks().mi_tiles;
+  for (int64_t t0 = 0; t0 < tiles; t0 += per) {
+    a.t0 = t0;
+    k_mi_scan<<<(unsigned)std::min<int64_t>(per, tiles - t0), kPtThreads, 0, s>>>(a);
+    FS_TRY(launch_check("k_mi_scan"));
   }
-
-  if (rc == FS_OK) {
-    // launches of about 2e11 lane operations each (a few milliseconds at the
-    // VALU peak), so that no launch holds the device for long: per tile and
-    // word 256 lanes run 16 ANDs and 16 popcount-accumulates
-    MiScanArgs a;
-    a.planes = dplanes, a.kcol = dkcol, a.n = n, a.p = p, a.P1p = P1p, a.W = W;
-    a.S = S, a.SP = SP, a.NB = NB, a.T = T, a.nbt = nbt, a.unit = unit;
-    a.only_y = nred == 0 && ncnt == 0;
-    a.red = dred, a.rel = drel, a.counts = dcnt;
-    const int64_t tiles = a.only_y ? nbt : nbt * (nbt + 1) / 2;
-    const double ops = 256.0 * 32.0 * (double)W;
-    int64_t per = (int64_t)std::max(1024.0, std::min(2e11 / ops, 1e9));
-    if (test_hooks().mi_tiles > 0) per = test_hooks().mi_tiles;
-    for (int64_t t0 = 0; t0 < tiles && rc == FS_OK; t0 += per) {
-      a.t0 = t0;
-      const unsigned blocks = (unsigned)std::min<int64_t>(per, tiles - t0);
-      k_mi_scan<<<blocks, kMiThreads, 0, s>>>(a);
-      if ((e = hipGetLastError()) != hipSuccess) fail("scan kernel", e);
-    }
+  FS_HIP(hipEventRecord(ev[3], s));
+  FS_HIP(hipMemcpyAsync(relevance, drel, (size_t)p * 8, hipMemcpyDeviceToHost, s));
+  if (nred) FS_HIP(hipMemcpyAsync(redundancy, dred, nred * 8, hipMemcpyDeviceToHost, s));
+  if (ncnt) FS_HIP(hipMemcpyAsync(counts_out, dcnt, ncnt * 4, hipMemcpyDeviceToHost, s));
+  FS_HIP(hipEventRecord(ev[4], s));
+  FS_HIP(hipStreamSynchronize(s));
+  for (int k = 0; k < 4; k++) {
+    float ms = -1.0f;
+    if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) g_mi_ms[k] = ms;
   }
-  mark(3);
-  if (rc == FS_OK &&
-      (e = hipMemcpyAsync(relevance, drel, (size_t)p * 8, hipMemcpyDeviceToHost, s)) != hipSuccess)
-    fail("download of the relevance", e);
-  if (rc == FS_OK && nred &&
-      (e = hipMemcpyAsync(redundancy, dred, nred * 8, hipMemcpyDeviceToHost, s)) != hipSuccess)
-    fail("download of the redundancy matrix", e);
-  if (rc == FS_OK && ncnt &&
-      (e = hipMemcpyAsync(counts_out, dcnt, ncnt * 4, hipMemcpyDeviceToHost, s)) != hipSuccess)
-    fail("download of the counts", e);
-  mark(4);
-  if (rc == FS_OK && (e = hipStreamSynchronize(s)) != hipSuccess) fail("scan", e);
-  if (s) (void)hipStreamSynchronize(s);
-  if (rc == FS_OK)
-    for (int k = 0; k < 4; k++) {
-      float ms = -1.0f;
-      if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) g_mi_ms[k] = ms;
-    }
   (void)hipGetLastError();
-  for (hipEvent_t v : ev)
-    if (v) (void)hipEventDestroy(v);
-  if (s) (void)hipStreamDestroy(s);
-  return rc;
+  return FS_OK;
 }
 
 }  // namespace gpu

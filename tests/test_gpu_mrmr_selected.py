@@ -1,7 +1,7 @@
 """Selection-only mRMR on the GPU (fs_mrmr.hip).  Every relevance and row
 entry must equal the GPU fs_mi_matrices entry bit for bit (k_mi_row runs
-k_mi_scan's epilogue in the same order) and lie within the suite's 1e-10 of the
-CPU backend's (the bound is derived in test_mi.py); the selection must be what
+pt_epilogue of fs_pairtab.h, k_mi_scan the same steps in fs_mi.hip) and lie within
+the suite's 1e-10 of the CPU backend's (derived in test_mi.py); the selection must be what
 the numpy loop selects from the GPU matrix, and two calls must give identical
 bits.  Shapes are the smallest at which the kernels can go wrong.  The row
 kernel takes 256 / NB^2 columns per workgroup (NB = ceil(states / 4)), y is one
