@@ -10,14 +10,16 @@ scikit-learn surface.  Scoring runs in hand-written HIP kernels for gfx950
 ``MDR`` is the reference's exhaustive k-way SNP interaction search, the usual
 second stage after a Relief filter; ``mRMR`` (with the
 ``fastselect_amd.mutual_information`` functions it is built on) drops
-redundant features in between, and ``CFS`` picks a subset by correlation with
-the class against correlation within the subset.
+redundant features in between, ``CFS`` picks a subset by correlation with
+the class against correlation within the subset, and ``JMI`` (JMI / CMIM) selects
+by joint relevance, which keeps features that matter only in interaction.
 
 Importing the package loads the native library; it fails loudly if the
 library has not been built.
 """
 from . import _lib, mutual_information
 from .CFS import CFS
+from .JMI import JMI
 from .MDR import MDR
 from .mRMR import mRMR
 from .MultiSURF import MultiSURF
@@ -31,13 +33,13 @@ from .TuRF import TuRF
 # attribute access cannot find them there and serialises the class by value:
 # dill does, and once a package that uses it (multiprocess, datasets) is
 # imported, so does joblib.dump.  Name the estimators by their public address.
-for _cls in (MultiSURF, ReliefF, SURF, TuRF, MDR, mRMR, CFS):
+for _cls in (MultiSURF, ReliefF, SURF, TuRF, MDR, mRMR, CFS, JMI):
     _cls.__module__ = __name__
 del _cls
 
 __version__ = "0.1.0"
 __all__ = ["ReliefF", "SURF", "MultiSURF", "SURFstar", "MultiSURFstar", "TuRF", "MDR", "mRMR",
-           "CFS"]
+           "CFS", "JMI"]
 
 
 def gpu_available() -> bool:

@@ -54,6 +54,7 @@ EXPORTED = (
     "fs_cfs_create", "fs_cfs_relevance", "fs_cfs_search", "fs_cfs_row", "fs_cfs_search_matrix",
     "fs_cfs_last_timing", "fs_cfs_destroy",
     "fs_mrmr_select", "fs_mrmr_search_matrix", "fs_mrmr_last_timing",
+    "fs_jmi_select", "fs_jmi_rows", "fs_jmi_search_matrix", "fs_jmi_last_timing",
 )
 
 
@@ -193,6 +194,13 @@ def _load() -> ctypes.CDLL:
     lib.fs_mrmr_search_matrix.argtypes = [_int, _int, _f64p, _f64p, _i64, _int, _i64, _i64p]
     lib.fs_mrmr_last_timing.argtypes = [_f64p]
     for name in ("fs_mrmr_select", "fs_mrmr_search_matrix", "fs_mrmr_last_timing"):
+        getattr(lib, name).restype = _int
+    lib.fs_jmi_select.argtypes = list(lib.fs_mrmr_select.argtypes)
+    lib.fs_jmi_rows.argtypes = [_int, _int, _u8p, _u8p, _i64, _i64, _int, _int, _i64p, _i64, _int,
+                                _f64p]
+    lib.fs_jmi_search_matrix.argtypes = list(lib.fs_mrmr_search_matrix.argtypes)
+    lib.fs_jmi_last_timing.argtypes = [_f64p]
+    for name in ("fs_jmi_select", "fs_jmi_rows", "fs_jmi_search_matrix", "fs_jmi_last_timing"):
         getattr(lib, name).restype = _int
     for name in ("fs_column_stats", "fs_multisurf_score", "fs_multisurf_score_rows",
                  "fs_plan_set_rows", "fs_relieff_score", "fs_surf_score",
@@ -979,4 +987,87 @@ def mrmr_last_timing():
     last GPU ``mrmr_select`` (``fs_mrmr_last_timing``; -1 where unavailable)."""
     v = np.full(5, -1.0)
     check(_lib.fs_mrmr_last_timing(_p(v, _f64p)))
+    return tuple(float(t) for t in v)
+
+
+JMI_METHODS = {"JMI": 0, "CMIM": 1}
+
+
+def _jmi_codes(codes, ycodes, unit):
+    x = np.ascontiguousarray(codes, dtype=np.uint8)
+    if x.ndim != 2:
+        raise ValueError("codes must be a 2-D array")
+    yv = np.ascontiguousarray(ycodes, dtype=np.uint8)
+    if yv.shape != (x.shape[0],):
+        raise ValueError("ycodes must have one entry per row of codes")
+    if unit not in MI_UNITS:
+        raise ValueError("unit must be 'bit' or 'nat'")
+    return x, yv
+
+
+def jmi_select(backend, codes, ycodes, n_states, k, method="JMI", unit="bit", n_jobs=-1,
+               device=0, want_rows=True):
+    """JMI / CMIM selection on lazy rows of joint relevance (``fs_jmi_select``):
+    the relevance, then per step one pick and one row
+    ``J(., s) = I(X_., X_s; y)``, k p joint tables in all.
+
+    ``codes`` (n x p) and ``ycodes`` (n) hold values in ``0..n_states-1``
+    (uint8).  Returns (selected int64 [k] in selection order, relevance
+    float64 [p], rows float64 [k, p] with ``rows[s] = J(., selected[s])``, or
+    None without ``want_rows``)."""
+    x, yv = _jmi_codes(codes, ycodes, unit)
+    n, p = x.shape
+    if method not in JMI_METHODS:
+        raise ValueError("method must be 'JMI' or 'CMIM'")
+    k = int(k)
+    rel = np.zeros(p, dtype=np.float64)
+    sel = np.zeros(max(k, 1), dtype=np.int64)
+    rows = np.zeros((k, p), dtype=np.float64) if want_rows and 1 <= k <= p else None
+    check(_lib.fs_jmi_select(_backend_code(backend), int(device), _p(x, _u8p), _p(yv, _u8p), n, p,
+                             int(n_states), MI_UNITS[unit], JMI_METHODS[method], k, int(n_jobs),
+                             _p(rel, _f64p), _p(sel, _i64p),
+                             None if rows is None else _p(rows, _f64p)))
+    return sel[:k], rel, rows
+
+
+def jmi_rows(backend, codes, ycodes, n_states, anchors, unit="bit", n_jobs=-1, device=0):
+    """The joint relevance of chosen anchor columns with every column
+    (``fs_jmi_rows``): float64 [m, p] with ``rows[t, c] = I(X_c, X_anchors[t]; y)``
+    and 0.0 at ``c == anchors[t]``."""
+    x, yv = _jmi_codes(codes, ycodes, unit)
+    n, p = x.shape
+    anc = np.ascontiguousarray(anchors, dtype=np.int64)
+    if anc.ndim != 1:
+        raise ValueError("anchors must be a vector of column indices")
+    m = anc.shape[0]
+    rows = np.zeros((m, p), dtype=np.float64)
+    check(_lib.fs_jmi_rows(_backend_code(backend), int(device), _p(x, _u8p), _p(yv, _u8p), n, p,
+                           int(n_states), MI_UNITS[unit], _p(anc, _i64p), m, int(n_jobs),
+                           _p(rows, _f64p)))
+    return rows
+
+
+def jmi_search_matrix(backend, relevance, joint, k, method="JMI", device=0):
+    """The greedy loop of JMI / CMIM on a caller's float64 ``relevance`` [p] and
+    symmetric ``joint`` [p, p] (``fs_jmi_search_matrix``).  Returns selected
+    int64 [k] in selection order."""
+    rel = np.ascontiguousarray(relevance, dtype=np.float64)
+    jm = np.ascontiguousarray(joint, dtype=np.float64)
+    p = rel.shape[0]
+    if rel.ndim != 1 or jm.shape != (p, p):
+        raise ValueError("relevance must be a vector of p entries and joint p x p")
+    if method not in JMI_METHODS:
+        raise ValueError("method must be 'JMI' or 'CMIM'")
+    k = int(k)
+    sel = np.zeros(max(k, 1), dtype=np.int64)
+    check(_lib.fs_jmi_search_matrix(_backend_code(backend), int(device), _p(rel, _f64p),
+                                    _p(jm, _f64p), p, JMI_METHODS[method], k, _p(sel, _i64p)))
+    return sel[:k]
+
+
+def jmi_last_timing():
+    """(upload, pack, relevance, rows, steps) milliseconds of this thread's
+    last GPU ``jmi_select`` (``fs_jmi_last_timing``; -1 where unavailable)."""
+    v = np.full(5, -1.0)
+    check(_lib.fs_jmi_last_timing(_p(v, _f64p)))
     return tuple(float(t) for t in v)

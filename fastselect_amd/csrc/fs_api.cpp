@@ -9,6 +9,7 @@
 #include "../../include/fastselect_amd.h"
 #include "fs_cfs.h"
 #include "fs_internal.h"
+#include "fs_jmi.h"
 #include "fs_mdr.h"
 #include "fs_mi.h"
 #include "fs_mrmr.h"
@@ -1192,6 +1193,63 @@ int fs_mrmr_last_timing(double* ms5) {
     return FS_EINVAL;
   }
   gpu::mrmr_last_timing(ms5);
+  return FS_OK;
+}
+
+int fs_jmi_select(int backend, int device, const uint8_t* codes, const uint8_t* ycodes, int64_t n,
+                  int64_t p, int n_states, int unit, int method, int64_t k, int n_jobs,
+                  double* relevance, int64_t* selected, double* rows) {
+  if (backend != FS_BACKEND_CPU && backend != FS_BACKEND_GPU) {
+    set_error("backend must be FS_BACKEND_CPU or FS_BACKEND_GPU");
+    return FS_EINVAL;
+  }
+  // the argument checks come before the device check, as in fs_mi_matrices
+  int rc = jmi_check_select(backend, codes, ycodes, n, p, n_states, unit, method, k, relevance,
+                            selected);
+  if (rc != FS_OK) return rc;
+  if ((rc = check_backend(backend, device)) != FS_OK) return rc;
+  if (backend == FS_BACKEND_GPU)
+    return gpu::jmi_select(device, codes, ycodes, n, p, n_states, unit, method, k, relevance,
+                           selected, rows);
+  return cpu::jmi_select(codes, ycodes, n, p, n_states, unit, method, k, n_jobs, relevance,
+                         selected, rows);
+}
+
+int fs_jmi_rows(int backend, int device, const uint8_t* codes, const uint8_t* ycodes, int64_t n,
+                int64_t p, int n_states, int unit, const int64_t* anchors, int64_t m, int n_jobs,
+                double* rows) {
+  if (backend != FS_BACKEND_CPU && backend != FS_BACKEND_GPU) {
+    set_error("backend must be FS_BACKEND_CPU or FS_BACKEND_GPU");
+    return FS_EINVAL;
+  }
+  int rc = jmi_check_rows(backend, codes, ycodes, n, p, n_states, unit, anchors, m, rows);
+  if (rc != FS_OK) return rc;
+  if ((rc = check_backend(backend, device)) != FS_OK) return rc;
+  if (backend == FS_BACKEND_GPU)
+    return gpu::jmi_rows(device, codes, ycodes, n, p, n_states, unit, anchors, m, rows);
+  return cpu::jmi_rows(codes, ycodes, n, p, n_states, unit, anchors, m, n_jobs, rows);
+}
+
+int fs_jmi_search_matrix(int backend, int device, const double* relevance, const double* joint,
+                         int64_t p, int method, int64_t k, int64_t* selected) {
+  if (backend != FS_BACKEND_CPU && backend != FS_BACKEND_GPU) {
+    set_error("backend must be FS_BACKEND_CPU or FS_BACKEND_GPU");
+    return FS_EINVAL;
+  }
+  int rc = jmi_check_matrix(relevance, joint, p, method, k, selected);
+  if (rc != FS_OK) return rc;
+  if ((rc = check_backend(backend, device)) != FS_OK) return rc;
+  if (backend == FS_BACKEND_GPU)
+    return gpu::jmi_search_matrix(device, relevance, joint, p, method, k, selected);
+  return cpu::jmi_search_matrix(relevance, joint, p, method, k, selected);
+}
+
+int fs_jmi_last_timing(double* ms5) {
+  if (!ms5) {
+    set_error("fs_jmi_last_timing: NULL output");
+    return FS_EINVAL;
+  }
+  gpu::jmi_last_timing(ms5);
   return FS_OK;
 }
 

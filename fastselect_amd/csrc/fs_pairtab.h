@@ -21,7 +21,9 @@
 // them).  What a pair's first lane does with the sum stays in each kernel's
 // own file.  k_mi_scan keeps its own staging (both sides of its tile come from
 // LDS) and, on a measurement, its own copy of the epilogue without the
-// transposition: see the note above that kernel.
+// transposition: see the note above that kernel.  fs_jmi.hip takes pt_row for
+// its relevance, pt_count and pt_block_best for k_jmi_row and its step kernels;
+// the three-way table's epilogue is that kernel's own.
 #pragma once
 
 #include "fs_gpu_internal.h"

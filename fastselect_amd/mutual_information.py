@@ -97,3 +97,41 @@ def calculate_mi_matrices(X, y, *, backend="auto", unit="bit", n_jobs=-1, device
     max_state = int(max(X_d.max(), y_d.max())) + 1
     where = _choose_backend(backend, max_state)
     return _lib.mi_matrices(where, X_d, y_d, max_state, unit=unit, n_jobs=n_jobs, device=device)
+
+
+_MAX_CLASSES_GPU = 4   # fs_jmi.h kJmiMaxClassesGpu: classes of y in the joint-relevance kernel
+
+
+def _choose_backend_joint(backend: str, max_state: int, n_classes: int) -> str:
+    """``_choose_backend`` extended by the joint-relevance kernel's class limit:
+    'auto' takes the CPU beyond either GPU limit, 'gpu' raises."""
+    if backend == "auto" and n_classes > _MAX_CLASSES_GPU:
+        return _choose_backend("cpu", max_state)
+    where = _choose_backend(backend, max_state)
+    if where == "gpu" and n_classes > _MAX_CLASSES_GPU:
+        raise RuntimeError(
+            f"GPU backend supports ≤{_MAX_CLASSES_GPU} classes of y for joint relevance "
+            f"(got {n_classes}); try backend='cpu'")
+    return where
+
+
+def calculate_joint_relevance(X, y, anchors, *, backend="auto", unit="bit", n_jobs=-1, device=0):
+    """Joint relevance ``I(X_c, X_a; y)`` of every column c with each anchor
+    column a of integer-coded X (n x p) and y (n): float64 [len(anchors), p],
+    0.0 where c == a (``fs_jmi_rows``).  Not a reference function: it is the
+    quantity the ``JMI`` estimator selects by."""
+    X = np.asarray(X)
+    y = np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1 or X.shape[0] != y.shape[0]:
+        raise ValueError("X must be 2‑D and y 1‑D with matching sample size")
+    X_d = _validate_discrete(X, "X")
+    y_d = _validate_discrete(y, "y")
+    anchors = np.atleast_1d(np.asarray(anchors))
+    if anchors.ndim != 1 or anchors.size < 1 or not np.issubdtype(anchors.dtype, np.integer):
+        raise ValueError("anchors must be a non-empty vector of column indices")
+    if anchors.min() < 0 or anchors.max() >= X.shape[1]:
+        raise ValueError("an anchor is outside 0..p-1")
+    max_state = int(max(X_d.max(), y_d.max())) + 1
+    where = _choose_backend_joint(backend, max_state, int(y_d.max()) + 1)
+    return _lib.jmi_rows(where, X_d, y_d, max_state, anchors, unit=unit, n_jobs=n_jobs,
+                         device=device)

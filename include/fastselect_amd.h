@@ -687,6 +687,65 @@ FS_API int fs_mrmr_search_matrix(int backend, int device, const double* relevanc
  * the benchmark tool. */
 FS_API int fs_mrmr_last_timing(double* ms5);
 
+/* ---- JMI and CMIM: selection on rows of joint relevance ------------------- */
+
+/*
+ * Greedy selection by the joint relevance J(f, s) = I(X_f, X_s; y) of a
+ * candidate with every selected feature, which sees a feature that matters
+ * only together with another one.  For columns lo < hi the table
+ * T[(a * kcol[hi] + b)][c] counts the samples with x_lo = a, x_hi = b, y = c;
+ * J is the mutual information of its rows (the joint state) and columns (y) by
+ * the float64 expressions of fs_mi_matrices in their order, so J(lo, hi)
+ * equals, bit for bit on the same backend, the relevance fs_mi_matrices gives
+ * the column x_lo * K + x_hi (K >= kcol[hi]).  J(f, f) = 0.0.
+ * Step 0 picks argmax relevance; after picking s the row J(., s) enters
+ *   JMI  (method 0, Yang & Moody):  acc[f] += J(f, s), from +0.0;
+ *   CMIM (method 1, Fleuret):       acc[f] = min(acc[f], J(f, s) - relevance[s]),
+ *                                   from +inf (I(X_f; y | X_s));
+ * step i >= 1 picks the unselected feature with the largest acc.  Among exact
+ * equals the lowest index wins; there is no closeness rule.  k p joint tables
+ * in all; nothing of size p x p is allocated.  The GPU backend queues all k
+ * steps on one stream and synchronises once.
+ *   relevance   [p]: I(X_f; y), the bits of fs_mi_matrices / fs_mrmr_select
+ *   selected    [k] in selection order
+ *   rows        NULL, or [k][p] float64 with rows[s][c] = J(c, selected[s]),
+ *               0.0 at c == selected[s]
+ *   n_jobs      CPU threads (-1 = all); ignored by the GPU backend
+ * codes, ycodes, n, p, n_states, unit: as fs_mi_matrices.  FS_EINVAL: as
+ * fs_mi_matrices, and k outside 1..p, method outside 0..1, NULL relevance /
+ * selected; on the CPU backend a joint table of more than 2^20 cells
+ * (max kcol^2 * kcol[y]); on the GPU backend more than 32 states or more than
+ * 4 classes of y.  FS_EOOM when the planes and rows do not fit (decided before
+ * any array is read).
+ */
+FS_API int fs_jmi_select(int backend, int device, const uint8_t* codes, const uint8_t* ycodes,
+                         int64_t n, int64_t p, int n_states, int unit, int method, int64_t k,
+                         int n_jobs, double* relevance, int64_t* selected, double* rows);
+/*
+ * The joint relevance of caller-chosen anchors through the same row code:
+ * rows[t][c] = J(c, anchors[t]), 0.0 at c == anchors[t].
+ *   anchors  [m] columns in 0..p-1, m >= 1
+ *   rows     [m][p] float64
+ * FS_EINVAL as fs_jmi_select, and an anchor outside 0..p-1, m < 1, NULL
+ * anchors / rows.
+ */
+FS_API int fs_jmi_rows(int backend, int device, const uint8_t* codes, const uint8_t* ycodes,
+                       int64_t n, int64_t p, int n_states, int unit, const int64_t* anchors,
+                       int64_t m, int n_jobs, double* rows);
+/*
+ * The same step code on a caller's relevance[p] and symmetric joint[p][p] (the
+ * picked feature's row is read): for tests that pin the tie and minimum rules,
+ * and for callers who hold a matrix already.
+ */
+FS_API int fs_jmi_search_matrix(int backend, int device, const double* relevance,
+                                const double* joint, int64_t p, int method, int64_t k,
+                                int64_t* selected);
+/* Milliseconds the calling thread's last GPU fs_jmi_select spent on upload,
+ * pack, relevance (with the first pick), rows and steps (HIP events; -1 where
+ * unavailable: above 64 steps the loop is timed as a whole, in `rows`), for
+ * the benchmark tool. */
+FS_API int fs_jmi_last_timing(double* ms5);
+
 #ifdef __cplusplus
 }
 #endif
