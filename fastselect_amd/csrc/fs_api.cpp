@@ -159,6 +159,8 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "mi_tiles") h.mi_tiles = value;
   else if (k == "list_cap") h.list_cap = value;
   else if (k == "cfs_rows_cap") h.cfs_rows_cap = value;
+  else if (k == "seg_len") h.seg_len = value;
+  else if (k == "pass2_generic") h.pass2_generic = value;
   else {
     set_error("fs_test_hook: unknown hook '" + k + "'");
     return FS_EINVAL;

@@ -146,6 +146,8 @@ struct TestHooks {
   int64_t mi_tiles = 0;        // >= 1: tiles per launch of the mutual-information scan (fs_mi.hip)
   int64_t list_cap = 0;        // >= 1: pairs the ambiguous-pair list holds at first (plan_create)
   int64_t cfs_rows_cap = 0;    // >= 1: rows the CFS row cache holds at first (fs_cfs.hip)
+  int64_t seg_len = 0;         // >= 1: tiles per pass-2 segment (shard_segments; small n computes 1)
+  int64_t pass2_generic = 0;   // 1: every k_score_sparse3 unit takes the plain-HIP walk
 };
 TestHooks& test_hooks();
 

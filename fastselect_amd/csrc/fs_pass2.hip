@@ -239,8 +239,10 @@ __global__ __launch_bounds__(256) void k_score(const float* __restrict__ xs, int
 // column jj = w + 16 c: 2 KB per stream, 64 KB per tile, every slot written
 // on every step.  No pair = +0.0 (never -0.0: the walk tests the bit
 // pattern).  Stream (t, h, w) starts at wrow + ((t * 2 + h) * 16 + w) *
-// kStreamWeights; the walk prefetches 128 bytes past a stream's end (the next
-// stream; the buffer ends with a spare tile).
+// kStreamWeights.  The walk reads no weight past a stream's end: its last step
+// requests the first 128 bytes of the same (half, wave) stream of the
+// segment's next tile (after the last tile: of that tile again).  The buffer
+// still ends with a spare, zeroed tile.
 constexpr int kHalf = 64;
 constexpr int kWaveCols = kTile / kSWaves;                  // 8
 constexpr int kStreamWeights = kWaveCols * kHalf;           // 512
@@ -290,9 +292,11 @@ __global__ __launch_bounds__(1024) void k_weights_sparse3(
 
 // The walk of one v3 stream in plain HIP: F features per lane (8: chunks
 // c = 0, 1 of the row, 4 each; 4: chunk 0 only), per-lane discrete flags.
-// Used for feature blocks holding discrete features; continuous blocks take
-// the generated loop of fs_sparse_asm.inc, which is this loop with wide
-// scalar weight loads, counted waits and a scalar test per weight.
+// Used for feature blocks holding discrete features (and for every block
+// under the pass2_generic test hook); continuous blocks take the generated
+// segment walk of fs_sparse_asm.inc, which is this loop with wide scalar
+// weight loads, counted waits and a scalar test per weight, and the tile loop
+// around it inside the same statement.
 template <int F>
 __device__ __forceinline__ void sparse3_rows_generic(const float4* __restrict__ As,
                                                      const float* __restrict__ wp,
@@ -344,12 +348,55 @@ __device__ __forceinline__ void sparse3_rows_generic(const float4* __restrict__ 
 // tail of a layout whose width is not a multiple of 512).  Lane l scores
 // features f0 + 4l + k and (F = 8) f0 + 256 + 4l + k, k = 0..3; partials go
 // to spart[(seg * 2 + h) * PW + f].
+//
+// A unit is walked in one of two ways, chosen once (the choice is constant
+// for a feature block):
+//  * every real feature of the block continuous: the row block is staged and
+//    ONE generated statement (fs_sparse_asm.inc, FS_SPARSE3_SEG_ASM_F8 / _F4)
+//    walks the segment's tiles, at most 64 per statement (one lane of the
+//    tile list each; the schedule caps a segment at 64, so the chunk loop
+//    around the statement runs once).  The tile loop, the
+//    fold into the f64 sums, the progress counter and the priority are inside
+//    the statement, in fixed registers: the per-tile statement it replaces
+//    left the compiler too few VGPRs for what lives across it (ScratchSize 68,
+//    three f64 sums and the tile list reloaded per tile behind vmcnt(0)
+//    waits, ~25 SGPRs restored by v_readlane on each side).  A tile's stream
+//    starts with its first 32 weights and its 8 B rows already requested by
+//    the previous tile's last step, and the LDS row ring runs through.
+//  * a block with discrete features: the C++ tile loop over
+//    sparse3_rows_generic, also taken by every unit under the pass2_generic
+//    test hook (same terms, same order, same fold points: the yardstick of
+//    the statement's bit equality).
+
+// Stage the 64 rows x 2 chunks of row block bi, half h (128 float4 per lane: 8
+// per wave, all requested before the first store -- one HBM latency per
+// segment, not eight) between two barriers.
+template <int F>
+__device__ __forceinline__ void sparse3_stage(float4* __restrict__ As, const float* __restrict__ xs,
+                                              int64_t PW, int bi, int64_t h, int64_t f0, int lane,
+                                              int wave) {
+  constexpr int C = F / 4;
+  __syncthreads();
+  const float* __restrict__ xa = xs + ((int64_t)bi * kTile + h * kHalf) * PW + f0 + 4 * lane;
+  constexpr int kPer = kHalf * 2 / kSWaves;
+  float4 v[kPer];
+#pragma unroll
+  for (int m = 0; m < kPer; m++) {
+    const int rc = wave + kSWaves * m, r = rc >> 1, c = rc & 1;
+    v[m] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (c < C && f0 + 256 * c + 4 * lane < PW) v[m] = *(const float4*)(xa + (int64_t)r * PW + 256 * c);
+  }
+#pragma unroll
+  for (int m = 0; m < kPer; m++) As[(wave + kSWaves * m) * 64 + lane] = v[m];
+  __syncthreads();
+}
+
 template <int F>
 __global__ __launch_bounds__(1024) void k_score_sparse3(
     const float* __restrict__ xs, int64_t PW, int64_t PC, const int2* __restrict__ tiles,
     const float* __restrict__ wrow, const int32_t* __restrict__ sched,
     const int32_t* __restrict__ seg_off, const int2* __restrict__ units, int64_t f_base,
-    double* __restrict__ spart) {
+    double* __restrict__ spart, int generic) {
   constexpr int C = F / 4;
   __shared__ float4 As[kHalf * 2 * 64];  // 64 rows x 2 chunks x 64 lanes (128 KB)
   const int lane = threadIdx.x & 63;
@@ -360,20 +407,22 @@ __global__ __launch_bounds__(1024) void k_score_sparse3(
   const int64_t f0 = f_base + fb * (64 * F);
   const int64_t t_begin = seg_off[seg];
   const int64_t t_end = seg_off[seg + 1];
-  bool disc[F];
-#pragma unroll
-  for (int c = 0; c < C; c++)
-#pragma unroll
-    for (int q = 0; q < 4; q++) disc[4 * c + q] = f0 + 256 * c + 4 * lane + q >= PC;
-  // the generated loop when every real feature of the block is continuous;
-  // features past PW stage zeros and their accumulators are discarded (their
-  // B values are read past the row's end: xs has kXsSlack floats of slack)
+  // the generated statement when every real feature of the block is
+  // continuous; features past PW stage zeros and their accumulators are
+  // discarded (their B values are read past the row's end: xs has kXsSlack
+  // floats of slack)
   const int64_t f_end = f0 + 64 * F < PW ? f0 + 64 * F : PW;
-  const bool fast = f_end <= PC;
+  const bool fast = f_end <= PC && !generic;
   const uint32_t lds_lane = (uint32_t)(uintptr_t)As + (uint32_t)lane * 16u;
   const uint32_t glb_lane = (uint32_t)lane * 16u;
   const int64_t bstride = kSWaves * PW;
   const uint32_t bstride_b = (uint32_t)(bstride * sizeof(float));
+  // what the final reduction needs of the unit, formed here so that little
+  // else is live across the walk: its row of spart from feature f0 on, and
+  // the number of real features from there
+  double* __restrict__ out = spart + (seg * 2 + h) * PW + f0;
+  int nvalid = (int)(PW - f0 < 64 * F ? PW - f0 : 64 * F);
+  asm volatile("" : "+s"(out), "+s"(nvalid));
   double s[F];
 #pragma unroll
   for (int q = 0; q < F; q++) s[q] = 0.0;
@@ -387,66 +436,73 @@ __global__ __launch_bounds__(1024) void k_score_sparse3(
   // ms at cfg4.  The scores do not change (same streams per wave, same order).
   __shared__ unsigned int wg_done;
   if (threadIdx.x == 0) wg_done = 0u;  // before the first staging barrier
-  unsigned int my_done = 0;
   // The segment's tile list, 64 tiles per lane-indexed load: tile k - t_begin
   // is lane (k - t_begin) % 64 of my_t / my_x / my_y (v_readlane per tile,
   // instead of two dependent scalar loads -- sched, then tiles -- per tile).
-  int my_t = 0, my_x = -1, my_y = 0;
-  int cur_bi = -1;
-  for (int64_t k = t_begin; k < t_end; k++) {
-    const int idx = (int)((k - t_begin) & 63);
-    if (idx == 0) {
-      const int64_t kk = k + lane;
-      my_t = kk < t_end ? sched[kk] : sched[k];
-      const int2 tt = tiles[my_t];
-      my_x = tt.x;
-      my_y = tt.y;
-    }
-    const int64_t t = __builtin_amdgcn_readlane(my_t, idx);
-    const int2 tl = make_int2(__builtin_amdgcn_readlane(my_x, idx), __builtin_amdgcn_readlane(my_y, idx));
-    if (tl.x != cur_bi) {  // once per segment: its tiles share one row block
-      __syncthreads();
-      // 64 rows x 2 chunks = 128 float4 per lane: 8 per wave, all requested
-      // before the first store (one HBM latency per segment, not eight)
-      const float* __restrict__ xa = xs + ((int64_t)tl.x * kTile + h * kHalf) * PW + f0 + 4 * lane;
-      constexpr int kPer = kHalf * 2 / kSWaves;
-      float4 v[kPer];
-#pragma unroll
-      for (int m = 0; m < kPer; m++) {
-        const int rc = wave + kSWaves * m, r = rc >> 1, c = rc & 1;
-        v[m] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (c < C && f0 + 256 * c + 4 * lane < PW) v[m] = *(const float4*)(xa + (int64_t)r * PW + 256 * c);
-      }
-#pragma unroll
-      for (int m = 0; m < kPer; m++) As[(wave + kSWaves * m) * 64 + lane] = v[m];
-      __syncthreads();
-      cur_bi = tl.x;
-    }
-    float acc[F];
-#pragma unroll
-    for (int q = 0; q < F; q++) acc[q] = 0.0f;
-    const float* __restrict__ wp = wrow + ((t * 2 + h) * kSWaves + wave) * kStreamWeights;
-    const float* __restrict__ xb = xs + ((int64_t)tl.y * kTile + wave) * PW + f0;
-    if (fast) {
-      const uint64_t wb = (uint64_t)(uintptr_t)wp;
-      const uint64_t bp = (uint64_t)(uintptr_t)xb;
+  if (fast) {
+    // stream (t, h, wave) = entw + t * 64 KB; B rows of column block y, column
+    // c of this wave = xsw + y * 8 bstride_b + c * bstride_b (bytes)
+    const uint64_t entw = (uint64_t)(uintptr_t)(wrow + (h * kSWaves + wave) * kStreamWeights);
+    const uint64_t xsw = (uint64_t)(uintptr_t)(xs + (int64_t)wave * PW + f0);
+    const uint32_t entw_lo = (uint32_t)entw, entw_hi = (uint32_t)(entw >> 32);
+    const uint32_t xsw_lo = (uint32_t)xsw, xsw_hi = (uint32_t)(xsw >> 32);
+    const uint32_t wgd = (uint32_t)(uintptr_t)&wg_done;
+    // once per segment: its tiles share one row block
+    if (t_begin < t_end) sparse3_stage<F>(As, xs, PW, tiles[sched[t_begin]].x, h, f0, lane, wave);
+    for (int k0 = (int)t_begin, k_end = (int)t_end; k0 < k_end; k0 += 64) {
+      const uint32_t done0 = (uint32_t)(k0 - (int)t_begin);
+      const int kk = k0 + lane;
+      const int my_t = sched[kk < k_end ? kk : k0];
+      const int my_y = tiles[my_t].y;
+      const uint32_t nt = (uint32_t)(k_end - k0 < 64 ? k_end - k0 : 64);
       if constexpr (F == 8) {
-        FS_SPARSE3_ASM_F8(acc, lds_lane, glb_lane, wb, bp, bstride_b);
+        FS_SPARSE3_SEG_ASM_F8(s, lds_lane, glb_lane, my_t, my_y, nt, entw_lo, entw_hi, xsw_lo, xsw_hi,
+                              bstride_b, wgd, done0);
       } else
-        FS_SPARSE3_ASM_F4(acc, lds_lane, glb_lane, wb, bp, bstride_b);
-    } else {
-      sparse3_rows_generic<F>(As, wp, xb + 4 * lane, bstride, lane, disc, acc);
+        FS_SPARSE3_SEG_ASM_F4(s, lds_lane, glb_lane, my_t, my_y, nt, entw_lo, entw_hi, xsw_lo, xsw_hi,
+                              bstride_b, wgd, done0);
     }
+  } else {
+    bool disc[F];
 #pragma unroll
-    for (int q = 0; q < F; q++) s[q] += (double)acc[q];
-    unsigned int tot = 0;
-    if (lane == 0) tot = atomicAdd(&wg_done, 1u) + 1u;
-    tot = __builtin_amdgcn_readfirstlane(tot);
-    ++my_done;
-    if (my_done * kSWaves < tot)
-      __builtin_amdgcn_s_setprio(2);
-    else
-      __builtin_amdgcn_s_setprio(0);
+    for (int c = 0; c < C; c++)
+#pragma unroll
+      for (int q = 0; q < 4; q++) disc[4 * c + q] = f0 + 256 * c + 4 * lane + q >= PC;
+    unsigned int my_done = 0;
+    int my_t = 0, my_x = -1, my_y = 0;
+    int cur_bi = -1;
+    for (int64_t k = t_begin; k < t_end; k++) {
+      const int idx = (int)((k - t_begin) & 63);
+      if (idx == 0) {
+        const int64_t kk = k + lane;
+        my_t = kk < t_end ? sched[kk] : sched[k];
+        const int2 tt = tiles[my_t];
+        my_x = tt.x;
+        my_y = tt.y;
+      }
+      const int64_t t = __builtin_amdgcn_readlane(my_t, idx);
+      const int2 tl = make_int2(__builtin_amdgcn_readlane(my_x, idx), __builtin_amdgcn_readlane(my_y, idx));
+      if (tl.x != cur_bi) {  // once per segment: its tiles share one row block
+        sparse3_stage<F>(As, xs, PW, tl.x, h, f0, lane, wave);
+        cur_bi = tl.x;
+      }
+      float acc[F];
+#pragma unroll
+      for (int q = 0; q < F; q++) acc[q] = 0.0f;
+      const float* __restrict__ wp = wrow + ((t * 2 + h) * kSWaves + wave) * kStreamWeights;
+      const float* __restrict__ xb = xs + ((int64_t)tl.y * kTile + wave) * PW + f0;
+      sparse3_rows_generic<F>(As, wp, xb + 4 * lane, bstride, lane, disc, acc);
+#pragma unroll
+      for (int q = 0; q < F; q++) s[q] += (double)acc[q];
+      unsigned int tot = 0;
+      if (lane == 0) tot = atomicAdd(&wg_done, 1u) + 1u;
+      tot = __builtin_amdgcn_readfirstlane(tot);
+      ++my_done;
+      if (my_done * kSWaves < tot)
+        __builtin_amdgcn_s_setprio(2);
+      else
+        __builtin_amdgcn_s_setprio(0);
+    }
   }
   // fixed-order reduction of the 16 waves' partials through the LDS block
   __syncthreads();
@@ -456,13 +512,13 @@ __global__ __launch_bounds__(1024) void k_score_sparse3(
   __syncthreads();
   if (wave < F) {
     const int q = wave;                                  // feature f0 + 256 (q/4) + 4 lane + q%4
-    const int64_t f = f0 + 256 * (q >> 2) + 4 * lane + (q & 3);
+    const int f = 256 * (q >> 2) + 4 * lane + (q & 3);
     const double* rr = red + q * kSWaves * 64 + lane;
     double v = 0.0;
 #pragma unroll
     for (int w = 0; w < kSWaves; w += 4)
       v += (rr[w * 64] + rr[(w + 1) * 64]) + (rr[(w + 2) * 64] + rr[(w + 3) * 64]);
-    if (f < PW) spart[(seg * 2 + h) * PW + f] = v;
+    if (f < nvalid) out[f] = v;
   }
 }
 
@@ -644,6 +700,8 @@ int shard_segments(Plan* g) {
   const int64_t wgs =
       g->sparse ? std::min<int64_t>(32768, std::max<int64_t>(1024, g->n_tiles * nfb / 16)) : 65536;
   g->seg_len = std::max<int64_t>(1, (g->n_tiles * nfb + wgs - 1) / wgs);
+  // tests: multi-tile segments of the sparse schedule at small n
+  if (g->sparse && test_hooks().seg_len >= 1) g->seg_len = test_hooks().seg_len;
   g->nseg = std::max<int64_t>(1, (g->n_tiles + g->seg_len - 1) / g->seg_len);
   if (Q.algo == ALGO_RELIEFF) return FS_OK;
   if (g->sparse) FS_TRY(build_sparse_schedule(g));  // its own segments (g->nseg)
@@ -697,15 +755,17 @@ int run_pass2(Plan* g, double* scores_dev) {
     // 512-feature blocks, then the tail block (build_sparse_schedule; one
     // F = 8 block is cheaper than two F = 4 ones -- cfg2, 448 features:
     // 0.24 -> 0.17 ms)
+    const int generic = test_hooks().pass2_generic == 1 ? 1 : 0;  // tests: every unit on the plain-HIP walk
     if (g->nunits8 > 0) {
       k_score_sparse3<8><<<(unsigned)g->nunits8, 64 * kSWaves, 0, g->stream>>>(
-          g->xs, Q.PW, Q.PC, g->tiles, g->wrow, g->sched.p, g->seg_off, g->units8.p, 0, g->spart.p);
+          g->xs, Q.PW, Q.PC, g->tiles, g->wrow, g->sched.p, g->seg_off, g->units8.p, 0, g->spart.p,
+          generic);
       FS_TRY(launch_check("k_score_sparse3<8>"));
     }
     if (g->nunits4 > 0) {
       k_score_sparse3<4><<<(unsigned)g->nunits4, 64 * kSWaves, 0, g->stream>>>(
           g->xs, Q.PW, Q.PC, g->tiles, g->wrow, g->sched.p, g->seg_off, g->units4, g->f_tail,
-          g->spart.p);
+          g->spart.p, generic);
       FS_TRY(launch_check("k_score_sparse3<4>"));
     }
   } else {

@@ -307,8 +307,9 @@ static int setup_shard(Plan* g, const std::vector<int32_t>& bi, const std::vecto
     rc = M.alloc(&g->Wt, (size_t)(g->n_tiles + 1) * kTile * kTile);
   } else if (g->sparse) {
     // 64 KB per tile (k_weights_sparse3 writes every slot on every step)
-    // and one spare tile: k_score_sparse3 prefetches the weights of a step
-    // past the end of a stream (never used; zeroed once all the same).
+    // and one spare, zeroed tile: k_score_sparse3's segment walk reads no
+    // weight past the last stream (its last step prefetches the next tile
+    // of the segment), the spare tile stays as a margin.
     const size_t count = (size_t)(g->n_tiles + 1) * kTileWeights;
     if (!(rc = M.alloc(&g->wrow, count)) && !(rc = M.alloc(&g->nnz, 1)) &&
         hipMemsetAsync(g->wrow + (size_t)g->n_tiles * kTileWeights, 0,

@@ -240,8 +240,10 @@ def gen(name="FS_SPARSE_STREAM_ASM", no_ds=False, same_stream=False, feats=4, sp
 
 
 HEADER = """// Generated by tools/gen_sparse_asm.py -- do not edit by hand.
-// Inner loops of k_score_sparse3 for continuous feature blocks (see V3_DOC in
-// the generator for the layout, the pipeline and the fixed registers).
+// Segment walks of k_score_sparse3 for continuous feature blocks: one
+// statement per (unit, chunk of <= 64 tiles).  See V3_DOC and V3SEG_DOC in
+// the generator for the layout, the pipeline, the fixed registers and the
+// highest byte every kind of load can touch.
 """
 
 # ---------------------------------------------------------------------------
@@ -1514,16 +1516,282 @@ def gen_v3(name, F=8):
 """
 
 
+# ---------------------------------------------------------------------------
+# v3 segment walk (shipped): the v3 row-major walk with the tile loop of a
+# (unit, segment) inside the statement
+# ---------------------------------------------------------------------------
+V3SEG_DOC = """
+Sparse v3 segment walk (k_score_sparse3, continuous feature blocks).  One
+statement per (unit, chunk of <= 64 tiles of its segment): the v3 walk of
+gen_v3 (same weights, same terms, same order, same counted waits) with the
+tile loop inside, so nothing the compiler owns is live across a tile
+boundary (the per-tile statement left it 128 - 97 VGPRs for eight f64 sums,
+the tile list and its own temporaries: three sums and the tile list went to
+scratch, ~25 SGPRs to v_writelane spills, each reloaded per tile behind its
+own vmcnt(0)).  Per tile, besides the walk:
+  * tile bookkeeping in SALU: tile k of the chunk is lane k of the
+    lane-indexed lists %[tiles] (weight tile t) and %[ys] (column block y),
+    picked with v_readlane_b32 and an SGPR index (written by SALU: no lane-
+    select hazard); stream base = entw + t * 64 KB, B pointer = xsw + y *
+    tstride (tstride = 8 bstride; 64-bit product).  The bases of tile k + 1 are formed while tile
+    k is walked (at the previous tile's end), so every load base was written
+    by SALU long before the load that uses it;
+  * the stream's last step (rows 60..63) requests, in place of the 128 bytes
+    past its end, the first 128 bytes of tile k + 1's stream of this wave
+    and half into the other SGPR set;
+  * in row 63, column c's block (or its skip) is followed at once by tile
+    k + 1's B loads of column c into the same registers (free from there);
+    the next tile's first row keeps gen_v3's per-column counted vmcnt (the
+    loads are issued in column order and nothing else uses vmcnt);
+  * the LDS ring runs through the boundary: the read issued before row 63
+    is consumed is row 0 of the same block = the next tile's first row;
+  * fold: per feature q v_cvt_f64_f32 of the tile partial, v_add_f64 into
+    sum q, partial zeroed; progress: lane 0 adds 1 (the others 0: EXEC stays
+    whole) to the workgroup's LDS counter with a returning add; the next
+    tile's bases; one lgkmcnt(0) (counter, row 0, the step's weights); then
+    s_setprio 2 when done * 16 < total, else 0 -- the C++ loop's order.
+After the last tile of the chunk the "next tile" is the last tile itself
+(index clamped to nt - 1): a re-read of 128 weight bytes and 8 B rows that
+lands before the statement's closing vmcnt(0) lgkmcnt(0) and is never used.
+
+Highest byte each kind of load can touch, and the allocation covering it:
+  * weights (s_load_dwordx16 x 2): base entw + t * 65536, entw = wrow +
+    (h * 16 + wave) * 2048 bytes, t a tile of the plan's schedule (t <
+    n_tiles); offsets 0 .. 2047 only (the last step's prefetch goes to the
+    NEXT tile's offset 0, not past the end).  Highest: wrow + n_tiles *
+    65536 - 1, inside wrow's (n_tiles + 1) * 64 KB.
+  * B rows (global_load_dwordx4): base xsw + y * tstride + c * bstride, xsw =
+    xs + (wave * PW + f0) floats, tstride = 128 PW floats, bstride = 16 PW
+    floats, c <= 7, y < n_pad / 128; per lane 16 l + 16 bytes, + 1024 at
+    F = 8.  Row index y * 128 + wave + 16 c <= n_pad - 1; the read covers
+    floats f0 .. f0 + 64 F - 1 of that row, past PW by less than 256 floats
+    (a partial block is at most 256 floats short: build_sparse_schedule).
+    Highest: xs + n_pad * PW + 255 floats, inside xs's (n_pad + 2) * PW +
+    kXsSlack (512) floats.  These are the addresses of the per-tile
+    statement: the walk adds no new kind.
+  * LDS rows (ds_read_b128): lds_lane + row * 2048 (+ 1024), row <= 63 (the
+    read after row 63 goes back to row 0): inside the 128 KB block.
+  * the only memory write: ds_add_rtn_u32 on the workgroup's counter.
+Hazards inside the string: every SGPR a load uses as base or offset is
+written by SALU (the v_readlane results pass through s_lshl / s_mul / s_add
+first; SALU reads of a VALU-written SGPR are interlocked); the v_readlane
+sources are statement inputs written before it; the counter's return is
+written by LDS and waited with lgkmcnt(0) before v_readfirstlane, followed
+by s_nop 0 pads around the VALU-SGPR-SALU hand-over for good measure.
+Registers (F = 8): v30..v93 B (8 x F), v94..v109 the ring (2 x F),
+v110..v117 sub scratch (doubles as the fold's f64 temporary, the counter's
+address, data and return), v118 row address, v119..v126 the tile's f32
+partials; the eight f64 sums are "+v" operands.  s[20:21] B pointer (next
+tile), s22 tile index, s23 weight offset (it also counts the bodies),
+s[24:25] stream base, s[26:27] next stream base, s36..s99 two weight sets;
+the temporaries of the prologue and the tile's end are s68..s73 of the
+second set, which holds nothing there.  The compiler keeps s0..s19,
+s28..s35 and s100 up.
+A/B knobs (profiles/pass2_seg/ab.txt; neither beat the plain form by more
+than the run-to-run spread, so the product uses neither): sub=4, a sub
+scratch of 4 registers with sub / fma in two groups of 4; one_lane=True, the
+counter add issued by lane 0 alone (EXEC = 1 around it, restored to all ones:
+every wave of the kernel is whole), which avoids the 64-lane same-address
+bank conflict of the plain form.
+"""
+
+
+def gen_v3seg(name, F=8, sub=None, one_lane=False):
+    R = F // 4                       # ds_read_b128 per row
+    NC = 8                           # columns per wave
+    SUB = sub or F                   # sub scratch registers per group
+    assert F % SUB == 0 and SUB >= 4
+    SET = [36, 68]
+    B0 = 30
+    RING = B0 + NC * F
+    TMP = RING + 2 * F
+    VA = TMP + SUB
+    ACC = VA + 1
+    VTOP = ACC + F                   # one past the last fixed VGPR
+    assert VTOP <= 127 and B0 % 2 == 0 and TMP % 2 == 0
+    T64, ADDR, ONE, RET = TMP, TMP + 2, TMP + 3, TMP + 2
+    ROWB = 2048                      # bytes of a row in the LDS block
+    BODY = 8                         # rows per unrolled body
+    BPTR, KT, OFF, BASE, NBASE = 20, 22, 23, 24, 26
+    # temporaries of the prologue and the tile's end, where the second weight
+    # set holds nothing (consumed by the last step, not yet requested again)
+    TY, KN, T, TT = SET[1], SET[1] + 1, SET[1] + 2, SET[1] + 4
+
+    def slot(r):
+        return RING + F * (r % 2)
+
+    def read(i, last):
+        # row i + 1 of the body; after the tile's last row: row 0 again (the
+        # next tile's first row)
+        a = slot(i + 1)
+        off = (i + 1) * ROWB if i + 1 < BODY else 0
+        L_ = []
+        if i + 1 == BODY:
+            L_.append(f"v_mov_b32 v{VA}, %[lds_lane]" if last else f"v_add_u32 v{VA}, 0x{BODY * ROWB:x}, v{VA}")
+        if F == 8:
+            L_.append(f"ds_read_b128 v[{a + 4}:{a + 7}], v{VA} offset:{off + 1024}")
+        L_.append(f"ds_read_b128 v[{a}:{a + 3}], v{VA}" + (f" offset:{off}" if off else ""))
+        return L_
+
+    lab = [0]
+
+    def block(i, c, w):
+        a, b = slot(i), B0 + F * c
+        lab[0] += 1
+        L_ = [f"s_cmp_eq_u32 s{w}, 0", f"s_cbranch_scc1 {100 + lab[0]}f"]
+        if i == 0:  # a tile's first row: column c's B loads (later bodies: already 0)
+            L_.append(f"s_waitcnt vmcnt({(NC - 1 - c) * R})")
+        for g in range(0, F, SUB):
+            L_ += [f"v_sub_f32 v{TMP + f - g}, v{a + f}, v{b + f}" for f in range(g, g + SUB)]
+            L_ += [f"v_fma_f32 v{ACC + f}, s{w}, |v{TMP + f - g}|, v{ACC + f}" for f in range(g, g + SUB)]
+        L_.append(f"{100 + lab[0]}:")
+        return L_
+
+    def bload(c):
+        d = B0 + F * c
+        L_ = [f"global_load_dwordx4 v[{d}:{d + 3}], %[glb_lane], s[{BPTR}:{BPTR + 1}]"]
+        if F == 8:
+            L_.append(f"global_load_dwordx4 v[{d + 4}:{d + 7}], %[glb_lane], s[{BPTR}:{BPTR + 1}] offset:1024")
+        if c + 1 < NC:
+            L_ += [f"s_add_u32 s{BPTR}, s{BPTR}, %[bstride]", f"s_addc_u32 s{BPTR + 1}, s{BPTR + 1}, 0"]
+        return L_
+
+    def step(x, last=False):
+        k, o = x % 2, 1 - x % 2
+        S = ["s_waitcnt lgkmcnt(0)"]
+        if last:  # the next tile's first step, not the bytes past this stream
+            S += [f"s_mov_b64 s[{BASE}:{BASE + 1}], s[{NBASE}:{NBASE + 1}]",
+                  f"s_load_dwordx16 s[{SET[o]}:{SET[o] + 15}], s[{BASE}:{BASE + 1}], 0x0",
+                  f"s_load_dwordx16 s[{SET[o] + 16}:{SET[o] + 31}], s[{BASE}:{BASE + 1}], 0x40"]
+        else:
+            S += [f"s_load_dwordx16 s[{SET[o]}:{SET[o] + 15}], s[{BASE}:{BASE + 1}], s{OFF}",
+                  f"s_add_u32 s{OFF}, s{OFF}, 64",
+                  f"s_load_dwordx16 s[{SET[o] + 16}:{SET[o] + 31}], s[{BASE}:{BASE + 1}], s{OFF}",
+                  f"s_add_u32 s{OFF}, s{OFF}, 64"]
+        for j in range(4):
+            i = 4 * x + j
+            S += read(i, last)
+            if j:  # the step's first row landed with the lgkmcnt(0) above
+                S.append(f"s_waitcnt lgkmcnt({R})")
+            for c in range(NC):
+                S += block(i, c, SET[k] + NC * j + c)
+                if last and i == BODY - 1:  # row 63: column c is done with its B values
+                    S += bload(c)
+            if i == 0:  # columns without a weight in the first row waited for nothing
+                S.append("s_waitcnt vmcnt(0)")
+        return S
+
+    def tile_bases(idx, base):
+        # stream base of the tile in lane idx -> s[base:base+1], its B pointer -> BPTR
+        return [f"v_readlane_b32 s{TY}, %[tiles], s{idx}",
+                "s_nop 0",
+                f"s_lshl_b32 s{TT}, s{TY}, 16",
+                f"s_lshr_b32 s{TT + 1}, s{TY}, 16",
+                f"s_add_u32 s{base}, %[entw_lo], s{TT}",
+                f"s_addc_u32 s{base + 1}, %[entw_hi], s{TT + 1}",
+                f"v_readlane_b32 s{TY}, %[ys], s{idx}",
+                "s_nop 0",
+                f"s_lshl_b32 s{T}, %[bstride], 3",       # a tile's 128 rows = 8 x this wave's column step
+                f"s_mul_i32 s{TT}, s{TY}, s{T}",
+                f"s_mul_hi_u32 s{TT + 1}, s{TY}, s{T}",
+                f"s_add_u32 s{BPTR}, %[xsw_lo], s{TT}",
+                f"s_addc_u32 s{BPTR + 1}, %[xsw_hi], s{TT + 1}"]
+
+    def next_bases():
+        # the tile after tile KT, clamped to the chunk's last
+        return [f"s_add_u32 s{KN}, s{KT}, 1",
+                f"s_sub_u32 s{T}, %[nt], 1",
+                f"s_min_u32 s{KN}, s{KN}, s{T}",
+                *tile_bases(KN, NBASE)]
+
+    lines = [f"s_mov_b32 s{KT}, 0",
+             *tile_bases(KT, BASE),
+             f"s_load_dwordx16 s[{SET[0]}:{SET[0] + 15}], s[{BASE}:{BASE + 1}], 0x0",
+             f"s_load_dwordx16 s[{SET[0] + 16}:{SET[0] + 31}], s[{BASE}:{BASE + 1}], 0x40"]
+    for c in range(NC):
+        lines += bload(c)
+    lines += [*[f"v_mov_b32 v{ACC + f}, 0" for f in range(F)],
+              f"v_mov_b32 v{VA}, %[lds_lane]"]
+    a = slot(0)
+    if F == 8:
+        lines.append(f"ds_read_b128 v[{a + 4}:{a + 7}], v{VA} offset:1024")
+    lines.append(f"ds_read_b128 v[{a}:{a + 3}], v{VA}")
+    lines += next_bases()
+    lines += ["50:",
+              f"s_mov_b32 s{OFF}, 128",
+              "7:"]
+    lines += step(0)
+    # the offset counts the bodies: 256 n after the first step of body n
+    lines += [f"s_cmp_eq_u32 s{OFF}, {256 * (64 // BODY)}", "s_cbranch_scc1 9f"]
+    lines += step(1)
+    lines += ["s_branch 7b", "9:"]
+    lines += step(1, last=True)
+    # the tile's end: fold, progress counter, the bases of the tile after next
+    for q in range(F):
+        lines += [f"v_cvt_f64_f32 v[{T64}:{T64 + 1}], v{ACC + q}",
+                  f"v_add_f64 %[s{q}], %[s{q}], v[{T64}:{T64 + 1}]",
+                  f"v_mov_b32 v{ACC + q}, 0"]
+    lines += [f"v_mov_b32 v{ADDR}, %[wgd]"]
+    if one_lane:  # A/B knob: the add issued by lane 0 alone (every wave of the kernel is whole)
+        lines += [f"v_mov_b32 v{ONE}, 1",
+                  "s_mov_b64 exec, 1",
+                  f"ds_add_rtn_u32 v{RET}, v{ADDR}, v{ONE}",
+                  "s_mov_b64 exec, -1"]
+    else:
+        lines += [f"v_min_u32 v{ONE}, 1, %[glb_lane]",      # 0 in lane 0, 1 elsewhere
+                  f"v_xor_b32 v{ONE}, 1, v{ONE}",
+                  f"ds_add_rtn_u32 v{RET}, v{ADDR}, v{ONE}"]
+    lines += [
+              f"s_add_u32 s{KT}, s{KT}, 1",
+              *next_bases(),
+              "s_waitcnt lgkmcnt(0)",
+              "s_nop 0",
+              f"v_readfirstlane_b32 s{TY}, v{RET}",
+              "s_nop 0",
+              f"s_add_u32 s{TY}, s{TY}, 1",                # the workgroup's total
+              f"s_add_u32 s{T}, s{KT}, %[done0]",          # this wave's tiles done
+              f"s_lshl_b32 s{T}, s{T}, 4",
+              f"s_cmp_lt_u32 s{T}, s{TY}",
+              "s_cbranch_scc1 64f",
+              "s_setprio 0",
+              "s_branch 65f",
+              "64:",
+              "s_setprio 2",
+              "65:",
+              f"s_cmp_lt_u32 s{KT}, %[nt]",
+              "s_cbranch_scc1 50b",
+              "s_waitcnt vmcnt(0) lgkmcnt(0)"]
+    body = "\n".join(f'      "{l}\\n"  \\' for l in lines)
+    vclob = ", ".join(f'"v{i}"' for i in range(B0, VTOP))
+    named = set()
+    for l in lines:
+        for lo, hi in re.findall(r"(?<![a-z_])s\[?(\d+)(?::(\d+)\])?", l):
+            named.update(range(int(lo), int(hi or lo) + 1))
+    sclob = ", ".join(f'"s{i}"' for i in sorted(named))
+    outs = ", ".join(f'[s{i}] "+v"(s_[{i}])' for i in range(F))
+    return f"""#define {name}(s_, lds_lane_, glb_lane_, tiles_, ys_, nt_, entw_lo_, entw_hi_, xsw_lo_, xsw_hi_, bstride_, wgd_, done0_)  \\
+  asm volatile(  \\
+{body}
+      : {outs}  \\
+      : [lds_lane] "v"(lds_lane_), [glb_lane] "v"(glb_lane_), [tiles] "v"(tiles_), [ys] "v"(ys_),  \\
+        [nt] "s"(nt_), [entw_lo] "s"(entw_lo_), [entw_hi] "s"(entw_hi_), [xsw_lo] "s"(xsw_lo_),  \\
+        [xsw_hi] "s"(xsw_hi_), [bstride] "s"(bstride_), [wgd] "s"(wgd_),  \\
+        [done0] "s"(done0_)  \\
+      : {vclob},  \\
+        {sclob}, "scc", "memory")
+"""
+
+
 if __name__ == "__main__":
-    # The product uses the v3 loops only (k_score_sparse3): the v2 loops
-    # (entry streams, one row read per entry) were retired for the row-major
-    # walk, the round-1/2 v1 loop in round 4 -- the functions above stay for
-    # the record, the microbenchmarks under tools/ubench and their logs in
-    # profiles/.
+    # The product uses the v3 segment walks only (k_score_sparse3): the
+    # per-tile v3 statement (gen_v3), the v2 loops (entry streams, one row
+    # read per entry) and the round-1/2 v1 loop were retired in turn -- the
+    # functions above stay for the record, the microbenchmarks under
+    # tools/ubench and their logs in profiles/.
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "fastselect_amd", "csrc",
                         "fs_sparse_asm.inc")
     text = HEADER
-    text += "\n" + gen_v3("FS_SPARSE3_ASM_F8", F=8)
-    text += "\n" + gen_v3("FS_SPARSE3_ASM_F4", F=4)
+    text += "\n" + gen_v3seg("FS_SPARSE3_SEG_ASM_F8", F=8)
+    text += "\n" + gen_v3seg("FS_SPARSE3_SEG_ASM_F4", F=4)
     open(path, "w").write(text)
     print("wrote", os.path.normpath(path))
