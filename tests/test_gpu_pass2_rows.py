@@ -174,3 +174,25 @@ def test_weighted_pairs_count(hooks):
     want = int(np.triu(near | near.T, 1).sum())
     assert 0.2 * n * (n - 1) / 2 < nz < 0.7 * n * (n - 1) / 2
     assert abs(nz - want) <= max(3, want // 2000)
+    # on grid data with the caller's thresholds (tests/pass2_np.py) no decision
+    # is in doubt: the count is the predicted one exactly
+    import pass2_np as R
+    from fastselect_amd import _lib
+    Xg, yg, isd, recip_g = R.grid_data(257, 300, 0, seed=9)
+    ng = len(Xg)
+    D = R.distances(Xg, isd)
+    H, M = R.counts_pow2(ng)
+    thr = R.patterns(D, ng)["q40"]
+    e = R.expected(Xg, yg, isd, thr, H, M, False, D=D)
+    R.check_exactness(Xg, isd, D, thr, H, M, e["W32"])
+    plan = _lib.Plan("gpu", Xg, yg.astype(np.float64), recip_g, isd)
+    try:
+        bufs = R.DevBufs(*Xg.shape)
+        plan.pass1(bufs.ptr("rs"))
+        bufs.sync()
+        R.select_and_score(plan, bufs, thr, R.pack_counts(H, M), plan.calibration()["SC"])
+        nz_grid = plan.weighted_pairs()
+    finally:
+        plan.close()
+    assert 0.2 * ng * (ng - 1) / 2 < e["weighted"] < 0.8 * ng * (ng - 1) / 2
+    assert nz_grid == e["weighted"]
