@@ -61,6 +61,47 @@ def lookup_table(X, y, interaction):
     return (ratios > threshold).astype(np.uint8)
 
 
+def summarise_folds(X, y, splits, best_rank, k, verbose=False):
+    """From every fold's best combination rank to the fitted model: the fold's
+    lookup table on its training rows, its test balanced accuracy, the
+    cross-validation consistency and the model choice (MDR.py:286-333).
+    ``fit`` and ``permutation_test`` both end here.  Only the k columns of a
+    fold's model are touched (``X[:, combo]`` before any row selection), so a
+    labelling costs O(folds * n * k).  Returns (best model, its CVC, its mean
+    test BA)."""
+    n_features = X.shape[1]
+    own = tuple(range(k))
+    fold_best_models = []
+    fold_test_bas = []
+    for fold_i, (train_idx, test_idx) in enumerate(splits):
+        best_combo = _lib.mdr_unrank(n_features, k, int(best_rank[fold_i]))
+        fold_best_models.append(best_combo)
+        Xc = X[:, best_combo]
+        lookup = lookup_table(Xc[train_idx], y[train_idx], own)
+        y_test = y[test_idx]
+        y_pred_test = lookup[cell_index(Xc[test_idx], own)]
+        tp = np.sum((y_test == 1) & (y_pred_test == 1))
+        tn = np.sum((y_test == 0) & (y_pred_test == 0))
+        n_pos = np.sum(y_test == 1)
+        n_neg = np.sum(y_test == 0)
+        sens = tp / n_pos if n_pos else 0
+        spec = tn / n_neg if n_neg else 0
+        test_ba = (sens + spec) / 2.0
+        fold_test_bas.append(test_ba)
+        if verbose:
+            print(f"  Fold {fold_i + 1}/{len(splits)}: best {best_combo}, Test BA = {test_ba:.4f}")
+
+    counts = Counter(fold_best_models)
+    max_cvc = counts.most_common(1)[0][1]
+    best_model, best_avg_ba = None, -1.0
+    for model in (m for m, c in counts.items() if c == max_cvc):
+        avg_ba = float(np.mean([fold_test_bas[i] for i, m in enumerate(fold_best_models)
+                                if m == model]))
+        if avg_ba > best_avg_ba:
+            best_avg_ba, best_model = avg_ba, model
+    return best_model, max_cvc, best_avg_ba
+
+
 class MDR(ClassifierMixin, BaseEstimator):
     """Multifactor dimensionality reduction on the MI355X or the CPU.
 
@@ -90,6 +131,9 @@ class MDR(ClassifierMixin, BaseEstimator):
     best_mean_testing_ba_ : float
     best_model_lookup_table_ : ndarray of uint8, shape (3**k,)
     classes_, n_features_in_, effective_backend_
+
+    ``permutation_test`` fits and adds the permutation null: ``p_value_``,
+    ``cvc_p_value_``, ``null_testing_ba_``, ``null_cvc_``, ``n_permutations_``.
     """
 
     def __init__(self, k: int = 2, cv: int = 10, backend: str = "auto", verbose: bool = False,
@@ -101,8 +145,9 @@ class MDR(ClassifierMixin, BaseEstimator):
         self.n_jobs = n_jobs
         self.device = device
 
-    def fit(self, X, y):
-        """Find the best k-way interaction by cross-validated MDR."""
+    def _validate(self, X, y):
+        """The checks of ``fit`` (MDR.py:220-244) and the reference's folds:
+        (X, y, k, fold ids, splits)."""
         X, y = check_X_y(X, y, dtype=np.uint8)
         self.classes_ = unique_labels(y)
         if len(self.classes_) != 2:
@@ -130,46 +175,75 @@ class MDR(ClassifierMixin, BaseEstimator):
         if self.verbose:
             print(f"CV with backend={self.effective_backend_.upper()}: {k}-way search over "
                   f"{_lib.mdr_combinations(n_features, k)} combos")
-        _, best_rank = _lib.mdr_scan(self.effective_backend_, X, y == 1, k, fold, len(splits),
-                                     device=self.device, n_jobs=self.n_jobs)
+        return X, y, k, fold, splits
 
-        fold_best_models = []
-        fold_test_bas = []
-        for fold_i, (train_idx, test_idx) in enumerate(splits):
-            best_combo = _lib.mdr_unrank(n_features, k, int(best_rank[fold_i]))
-            fold_best_models.append(best_combo)
-            lookup = lookup_table(X[train_idx], y[train_idx], best_combo)
-            y_test = y[test_idx]
-            y_pred_test = lookup[cell_index(X[test_idx], best_combo)]
-            tp = np.sum((y_test == 1) & (y_pred_test == 1))
-            tn = np.sum((y_test == 0) & (y_pred_test == 0))
-            n_pos = np.sum(y_test == 1)
-            n_neg = np.sum(y_test == 0)
-            sens = tp / n_pos if n_pos else 0
-            spec = tn / n_neg if n_neg else 0
-            test_ba = (sens + spec) / 2.0
-            fold_test_bas.append(test_ba)
-            if self.verbose:
-                print(f"  Fold {fold_i + 1}/{self.cv}: best {best_combo}, Test BA = {test_ba:.4f}")
-
-        counts = Counter(fold_best_models)
-        max_cvc = counts.most_common(1)[0][1]
-        best_model, best_avg_ba = None, -1.0
-        for model in (m for m, c in counts.items() if c == max_cvc):
-            avg_ba = float(np.mean([fold_test_bas[i] for i, m in enumerate(fold_best_models)
-                                    if m == model]))
-            if avg_ba > best_avg_ba:
-                best_avg_ba, best_model = avg_ba, model
-
-        self.best_interaction_ = best_model
-        self.best_cvc_ = max_cvc
-        self.best_mean_testing_ba_ = best_avg_ba
+    def _set_model(self, X, y, model, cvc, mean_ba):
+        self.best_interaction_ = model
+        self.best_cvc_ = cvc
+        self.best_mean_testing_ba_ = mean_ba
         if self.verbose:
             print("\nFit Complete")
             print(f"Best interaction: {self.best_interaction_}")
             print(f"CVC: {self.best_cvc_}/{self.cv}")
             print(f"Mean testing BA: {self.best_mean_testing_ba_:.4f}")
         self.best_model_lookup_table_ = lookup_table(X, y, self.best_interaction_)
+
+    def fit(self, X, y):
+        """Find the best k-way interaction by cross-validated MDR."""
+        X, y, k, fold, splits = self._validate(X, y)
+        _, best_rank = _lib.mdr_scan(self.effective_backend_, X, y == 1, k, fold, len(splits),
+                                     device=self.device, n_jobs=self.n_jobs)
+        self._set_model(X, y, *summarise_folds(X, y, splits, best_rank, k, self.verbose))
+        return self
+
+    def permutation_test(self, X, y, n_permutations=1000, random_state=None):
+        """``fit`` plus the permutation null of its two statistics.
+
+        The whole search runs on the observed phenotype and on
+        ``n_permutations`` permuted ones in one ``fs_mdr_scan_labels`` call.
+        The case flags are permuted *within each fold* (``rng =
+        np.random.default_rng(random_state)``; labellings in order, folds in
+        order, ``rng.permutation`` of the fold's flags), so every fold keeps
+        its class counts, the folds stay stratified for every labelling and
+        are the ones ``fit`` draws.  Sets every attribute ``fit`` sets, with
+        the same values, and
+
+        null_testing_ba_ : ndarray of float64, shape (n_permutations,)
+            ``best_mean_testing_ba_`` of each permuted labelling.
+        null_cvc_ : ndarray of int, shape (n_permutations,)
+        p_value_ : float
+            ``(1 + #{null_testing_ba_ >= best_mean_testing_ba_}) / (1 + n_permutations)``.
+        cvc_p_value_ : float
+            The same on the cross-validation consistency.
+        n_permutations_ : int
+        """
+        n_perm = int(n_permutations)
+        if n_perm < 1:
+            raise ValueError(f"n_permutations must be >= 1. Got {n_permutations}")
+        X, y, k, fold, splits = self._validate(X, y)
+        rng = np.random.default_rng(random_state)
+        labels = np.empty((n_perm + 1, X.shape[0]), dtype=np.uint8)
+        labels[0] = y == 1
+        for b in range(1, n_perm + 1):
+            for _, test_idx in splits:
+                labels[b, test_idx] = rng.permutation(labels[0, test_idx])
+        _, best_rank = _lib.mdr_scan_labels(self.effective_backend_, X, labels, k, fold,
+                                            len(splits), device=self.device, n_jobs=self.n_jobs)
+
+        self._set_model(X, y, *summarise_folds(X, y, splits, best_rank[0], k, self.verbose))
+        # a permuted phenotype in y's own two labels: 1 for a case
+        others = self.classes_[self.classes_ != 1]
+        control = others[0] if len(others) else self.classes_[0]
+        null_ba = np.empty(n_perm, dtype=np.float64)
+        null_cvc = np.empty(n_perm, dtype=np.int64)
+        for b in range(1, n_perm + 1):
+            yb = np.where(labels[b] != 0, np.asarray(1, dtype=y.dtype), control)
+            _, null_cvc[b - 1], null_ba[b - 1] = summarise_folds(X, yb, splits, best_rank[b], k)
+        self.null_testing_ba_ = null_ba
+        self.null_cvc_ = null_cvc
+        self.n_permutations_ = n_perm
+        self.p_value_ = (1 + int(np.sum(null_ba >= self.best_mean_testing_ba_))) / (1 + n_perm)
+        self.cvc_p_value_ = (1 + int(np.sum(null_cvc >= self.best_cvc_))) / (1 + n_perm)
         return self
 
     def predict(self, X):

@@ -49,7 +49,8 @@ EXPORTED = (
     "fs_plan_destroy", "fs_multisurf_score_devices", "fs_relieff_score_devices",
     "fs_surf_score_devices", "fs_set_accumulation", "fs_get_accumulation", "fs_test_hook",
     "fs_multisurf_score_ex", "fs_relieff_score_ex", "fs_surf_score_ex",
-    "fs_mdr_scan", "fs_mdr_combinations", "fs_mdr_unrank",
+    "fs_mdr_scan", "fs_mdr_scan_labels", "fs_mdr_labels_last_timing", "fs_mdr_combinations",
+    "fs_mdr_unrank",
     "fs_mi_matrices", "fs_mi_last_timing",
     "fs_cfs_create", "fs_cfs_relevance", "fs_cfs_search", "fs_cfs_row", "fs_cfs_search_matrix",
     "fs_cfs_last_timing", "fs_cfs_destroy",
@@ -168,6 +169,11 @@ def _load() -> ctypes.CDLL:
     lib.fs_mdr_scan.argtypes = [_int, _int, _u8p, _i64, _i64, _u8p, _int, _i32p, _int, _int, _f32p,
                                 _i64p, _f32p]
     lib.fs_mdr_scan.restype = _int
+    lib.fs_mdr_scan_labels.argtypes = [_int, _int, _u8p, _i64, _i64, _u8p, _int, _int, _i32p, _int,
+                                       _int, _f32p, _i64p, _f32p]
+    lib.fs_mdr_scan_labels.restype = _int
+    lib.fs_mdr_labels_last_timing.argtypes = [_f64p]
+    lib.fs_mdr_labels_last_timing.restype = _int
     lib.fs_mdr_combinations.argtypes = [_i64, _int, _i64p]
     lib.fs_mdr_combinations.restype = _int
     lib.fs_mdr_unrank.argtypes = [_i64, _int, _i64, _i32p]
@@ -798,6 +804,51 @@ def mdr_scan(backend, x, is_case, k, fold=None, n_folds=0, device=0, n_jobs=-1, 
                            int(n_jobs), _p(best_ba, _f32p), _p(best_rank, _i64p),
                            None if ba is None else _p(ba, _f32p)))
     return (best_ba, best_rank, ba) if want_ba else (best_ba, best_rank)
+
+
+def mdr_scan_labels(backend, x, labels, k, fold=None, n_folds=0, device=0, n_jobs=-1,
+                    want_ba=False):
+    """``mdr_scan`` for B labellings of one genotype matrix in one pass
+    (``fs_mdr_scan_labels``): ``labels`` is B x n, nonzero = case, and the
+    folds are shared.  Returns (best_ba float32[B, F], best_rank int64[B, F])
+    with F = max(n_folds, 1), plus the B x F x C(p,k) float32 array of every BA
+    when ``want_ba`` (small jobs only).  Row b equals ``mdr_scan(backend, x,
+    labels[b], ...)`` bit for bit."""
+    x = np.ascontiguousarray(x, dtype=np.uint8)
+    if x.ndim != 2:
+        raise ValueError("x must be a 2-D array")
+    n, p = x.shape
+    lab = np.ascontiguousarray(labels, dtype=np.uint8)
+    if lab.ndim != 2 or lab.shape[1] != n:
+        raise ValueError("labels must be 2-D with one column per row of x")
+    nb = lab.shape[0]
+    fv = None
+    if fold is not None:
+        fv = np.ascontiguousarray(fold, dtype=np.int32)
+        if fv.shape != (n,):
+            raise ValueError("fold must have one entry per row of x")
+    else:
+        n_folds = 0
+    nf = max(int(n_folds), 1)
+    best_ba = np.zeros((nb, nf), dtype=np.float32)
+    best_rank = np.zeros((nb, nf), dtype=np.int64)
+    ba = None
+    if want_ba:
+        ba = np.zeros((nb, nf, mdr_combinations(p, k)), dtype=np.float32)
+    check(_lib.fs_mdr_scan_labels(_backend_code(backend), int(device), _p(x, _u8p), n, p,
+                                  _p(lab, _u8p), nb, int(k),
+                                  None if fv is None else _p(fv, _i32p), int(n_folds), int(n_jobs),
+                                  _p(best_ba, _f32p), _p(best_rank, _i64p),
+                                  None if ba is None else _p(ba, _f32p)))
+    return (best_ba, best_rank, ba) if want_ba else (best_ba, best_rank)
+
+
+def mdr_labels_last_timing():
+    """(upload, pack, scan, download) milliseconds of this thread's last GPU
+    ``mdr_scan_labels`` (``fs_mdr_labels_last_timing``; -1 where unavailable)."""
+    v = np.full(4, -1.0)
+    check(_lib.fs_mdr_labels_last_timing(_p(v, _f64p)))
+    return tuple(float(t) for t in v)
 
 
 MI_UNITS = {"bit": 0, "nat": 1}

@@ -1032,6 +1032,31 @@ int fs_mdr_scan(int backend, int device, const uint8_t* x, int64_t n, int64_t p,
                        ba_out);
 }
 
+int fs_mdr_scan_labels(int backend, int device, const uint8_t* x, int64_t n, int64_t p,
+                       const uint8_t* labels, int n_labelings, int k, const int32_t* fold,
+                       int n_folds, int n_jobs, float* best_ba, int64_t* best_rank, float* ba_out) {
+  int rc = check_backend(backend, device);
+  if (rc != FS_OK) return rc;
+  int64_t count = 0;
+  if ((rc = mdr_check_labels(x, n, p, labels, n_labelings, k, fold, n_folds, best_ba, best_rank,
+                             &count)) != FS_OK)
+    return rc;
+  if (backend == FS_BACKEND_GPU)
+    return gpu::mdr_scan_labels(device, x, n, p, labels, n_labelings, k, fold, n_folds, count,
+                                best_ba, best_rank, ba_out);
+  return cpu::mdr_scan_labels(x, n, p, labels, n_labelings, k, fold, n_folds, n_jobs, count,
+                              best_ba, best_rank, ba_out);
+}
+
+int fs_mdr_labels_last_timing(double* ms4) {
+  if (!ms4) {
+    set_error("fs_mdr_labels_last_timing: NULL output");
+    return FS_EINVAL;
+  }
+  gpu::mdr_labels_last_timing(ms4);
+  return FS_OK;
+}
+
 int fs_mdr_combinations(int64_t p, int k, int64_t* count) {
   if (!count || k < 1 || k > kMdrMaxK || p < k) {
     set_error("fs_mdr_combinations: need count, k in 1..6 and p >= k");

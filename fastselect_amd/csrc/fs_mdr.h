@@ -143,15 +143,43 @@ int mdr_check(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, in
               const int32_t* fold, int n_folds, const float* best_ba, const int64_t* best_rank,
               int64_t* count);
 
+// fs_mdr_scan_labels: many labellings of one genotype matrix.  The class is
+// not part of this layout: segment f holds every sample whose test fold is f,
+// padded to whole words (seg_off has F + 1 entries; tc / tn stay empty).  A
+// cell's cases in fold f under labelling b are popcount(cell & label words of
+// b) over f's words and its controls are the cell's count minus that: the
+// same integers as the (class, fold) layout gives, so the same BA bits.
+constexpr int kMdrMaxLabelings = 65535;
+
+int mdr_fold_layout(int64_t n, const int32_t* fold, int n_folds, int wordbits, MdrLayout& L);
+
+// Training cases / controls of fold f under labelling b, at [f * n_labelings + b].
+void mdr_label_totals(int64_t n, const uint8_t* labels, int n_labelings, const MdrLayout& L,
+                      int n_jobs, std::vector<uint32_t>& tc, std::vector<uint32_t>& tn);
+
+// The checks of mdr_check plus those on the labellings.
+int mdr_check_labels(const uint8_t* x, int64_t n, int64_t p, const uint8_t* labels,
+                     int n_labelings, int k, const int32_t* fold, int n_folds,
+                     const float* best_ba, const int64_t* best_rank, int64_t* count);
+
 namespace cpu {
 int mdr_scan(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int k,
              const int32_t* fold, int n_folds, int n_jobs, int64_t count, float* best_ba,
              int64_t* best_rank, float* ba_out);
+int mdr_scan_labels(const uint8_t* x, int64_t n, int64_t p, const uint8_t* labels,
+                    int n_labelings, int k, const int32_t* fold, int n_folds, int n_jobs,
+                    int64_t count, float* best_ba, int64_t* best_rank, float* ba_out);
 }
 namespace gpu {
 int mdr_scan(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int k,
              const int32_t* fold, int n_folds, int64_t count, float* best_ba, int64_t* best_rank,
              float* ba_out);
+int mdr_scan_labels(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* labels,
+                    int n_labelings, int k, const int32_t* fold, int n_folds, int64_t count,
+                    float* best_ba, int64_t* best_rank, float* ba_out);
+// Milliseconds of the calling thread's last GPU mdr_scan_labels: upload, pack,
+// scan with the reduction, download (HIP events on the call's stream).
+void mdr_labels_last_timing(double* ms4);
 }
 
 }  // namespace fs

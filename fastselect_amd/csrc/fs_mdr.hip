@@ -21,6 +21,9 @@
 //                atomics: the result is deterministic.  A block owns a
 //                contiguous run of ranks: a lane unranks once and then steps
 //                its combination by the block size (mdr_advance).
+//
+// The GPU backend of fs_mdr_scan_labels (one lane per labelling) follows
+// below, with its own layout and kernels.
 #include "fs_gpu_internal.h"
 #include "fs_mdr.h"
 
@@ -34,6 +37,25 @@ constexpr int kMdrThreads = 256;
 constexpr int kMdrMaxBlocks = 2048;
 constexpr uint32_t kNoIter = 0xffffffffu;
 
+// The 32 samples at perm[0..32) of column j -> the column's three genotype
+// words; true when a genotype is above 2.
+__device__ __forceinline__ bool pack_word(const uint8_t* __restrict__ x, int64_t p,
+                                          const int32_t* __restrict__ perm, int64_t j,
+                                          uint32_t& b0, uint32_t& b1, uint32_t& b2) {
+  b0 = b1 = b2 = 0;
+  bool wrong = false;
+  for (int b = 0; b < 32; b++) {
+    const int32_t i = perm[b];
+    if (i < 0) continue;
+    const uint8_t g = x[(size_t)i * p + j];
+    b0 |= (uint32_t)(g == 0) << b;
+    b1 |= (uint32_t)(g == 1) << b;
+    b2 |= (uint32_t)(g == 2) << b;
+    wrong |= g > 2;
+  }
+  return wrong;
+}
+
 // One thread per (word, column): 32 samples of one column -> three words.
 __global__ __launch_bounds__(256) void k_mdr_pack(const uint8_t* __restrict__ x, int64_t p,
                                                   const int32_t* __restrict__ perm, int64_t words,
@@ -42,17 +64,8 @@ __global__ __launch_bounds__(256) void k_mdr_pack(const uint8_t* __restrict__ x,
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t w = blockIdx.y;
   if (j >= p || w >= words) return;
-  uint32_t b0 = 0, b1 = 0, b2 = 0;
-  bool wrong = false;
-  for (int b = 0; b < 32; b++) {
-    const int32_t i = perm[w * 32 + b];
-    if (i < 0) continue;
-    const uint8_t g = x[(size_t)i * p + j];
-    b0 |= (uint32_t)(g == 0) << b;
-    b1 |= (uint32_t)(g == 1) << b;
-    b2 |= (uint32_t)(g == 2) << b;
-    wrong |= g > 2;
-  }
+  uint32_t b0, b1, b2;
+  const bool wrong = pack_word(x, p, perm + w * 32, j, b0, b1, b2);
   planes[((size_t)w * 3 + 0) * p + j] = b0;
   planes[((size_t)w * 3 + 1) * p + j] = b1;
   planes[((size_t)w * 3 + 2) * p + j] = b2;
@@ -207,6 +220,279 @@ void launch_scan(const MdrScanArgs& a, int blocks, hipStream_t s) {
     k_mdr_scan<K, kMdrG><<<blocks, kMdrThreads, 0, s>>>(a);
 }
 
+// ---- fs_mdr_scan_labels: one lane per labelling ---------------------------
+//
+//   The fold-only layout (mdr_fold_layout) is built on quads, four words =
+//   128 samples: a fold's segment is a whole number of quads, so every quad
+//   of a plane is one aligned 16-byte load.
+//   k_mdr_pack_cols    as k_mdr_pack on that layout, word index fastest
+//   k_mdr_pack_labels  labels (bytes) -> y[(q * B + b) * 4 + i]: word i of quad
+//                      q under labelling b; within a quad the labelling index
+//                      is fastest, so a wave's 16-byte loads are consecutive
+//   k_mdr_scan_labels  a wave takes one combination at a time and its 64 lanes
+//                      take 64 labellings.  The combination is wave-uniform,
+//                      so the plane loads, the ANDs of the k columns and the
+//                      per-(genotype, fold) cell counts are scalar work done
+//                      once for 64 labellings; a lane adds popcount(cell &
+//                      its label word) and keeps case counts only (controls =
+//                      cell count - cases).  The four waves of a block take
+//                      interleaved ranks of the block's run; the block merges
+//                      (max BA, min rank) per (labelling, fold) into its slot
+//   k_mdr_labels_reduce  the slots of all blocks -> [B][F], on the device
+constexpr int kMdrLabWaves = kMdrThreads / 64;
+constexpr int kMdrLabMaxBlocks = 1024;         // rank runs (grid.x) per launch
+constexpr size_t kMdrLabMaxSlots = (size_t)1 << 24;
+
+// k_mdr_pack with the word index fastest: planes[(j * 3 + g) * words + w].
+// A wave of the labels scan reads one column's words in a row through the
+// scalar cache.  One thread per (word, column); perm covers all the words.
+__global__ __launch_bounds__(256) void k_mdr_pack_cols(const uint8_t* __restrict__ x, int64_t p,
+                                                       const int32_t* __restrict__ perm,
+                                                       int64_t words, int64_t w0,
+                                                       uint32_t* __restrict__ planes,
+                                                       int* __restrict__ bad) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t w = w0 + blockIdx.y;
+  if (j >= p || w >= words) return;
+  uint32_t b0, b1, b2;
+  const bool wrong = pack_word(x, p, perm + w * 32, j, b0, b1, b2);
+  planes[((size_t)j * 3 + 0) * words + w] = b0;
+  planes[((size_t)j * 3 + 1) * words + w] = b1;
+  planes[((size_t)j * 3 + 2) * words + w] = b2;
+  if (wrong) atomicOr(bad, 1);
+}
+
+// One thread per (word, labelling).
+__global__ __launch_bounds__(256) void k_mdr_pack_labels(const uint8_t* __restrict__ labels,
+                                                         int64_t n, int B,
+                                                         const int32_t* __restrict__ perm,
+                                                         int64_t words, int64_t w0,
+                                                         uint32_t* __restrict__ y) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t w = w0 + blockIdx.y;
+  if (b >= B || w >= words) return;
+  uint32_t bits = 0;
+  for (int i = 0; i < 32; i++) {
+    const int32_t s = perm[w * 32 + i];
+    if (s >= 0) bits |= (uint32_t)(labels[(size_t)b * n + s] != 0) << i;
+  }
+  y[((size_t)(w >> 2) * B + b) * 4 + (w & 3)] = bits;
+}
+
+__global__ __launch_bounds__(256) void k_mdr_labels_fill(uint32_t* __restrict__ bits,
+                                                         int64_t* __restrict__ rank, size_t slots) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < slots) bits[i] = 0, rank[i] = kMdrNoRank;
+}
+
+// A quad: four words = 128 samples.  The planes are read-only for the whole
+// kernel and every wave reads them at wave-uniform addresses: loads through
+// the constant address space stay on the scalar unit whatever the kernel
+// stores elsewhere.
+typedef uint32_t Quad __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) Quad PlaneQuad;
+
+struct MdrLabelArgs {
+  const Quad* planes;      // [(column * 3 + genotype) * quads + q]
+  int64_t p, quads;
+  const Quad* y;            // quads x B
+  const int32_t* seg_off;   // F + 1 quad offsets
+  const uint32_t* tc;       // F x B training cases
+  const uint32_t* tn;       // F x B training controls
+  int B, b0;                // grid.y * 64 + lane + b0 is the lane's labelling
+  int F, f0, gn, sub;       // this launch scores folds [f0, f0 + gn)
+  int64_t count, r0, r1;    // C(p,k) and this launch's rank range
+  int64_t per_block;        // ranks per block, a multiple of the waves per block
+  float* ba_out;            // NULL or B x F x count
+  uint32_t* part_bits;      // blocks x F x B
+  int64_t* part_rank;
+};
+
+__device__ __forceinline__ uint32_t popc4(Quad v) {
+  return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
+}
+
+// Over the quads [q0, q1): the cell's count (wave-uniform) and the lane's
+// case count for the last column's three genotypes.  A plane's quad is one
+// 16-byte scalar load and the lane's four label words one 16-byte vector load.
+template <int K>
+__device__ __forceinline__ void count3_labels(PlaneQuad* const* pre, PlaneQuad* last,
+                                              size_t Q, const Quad* y, size_t B, uint32_t b,
+                                              uint32_t q0, uint32_t q1, uint32_t* n, uint32_t& a0,
+                                              uint32_t& a1, uint32_t& a2) {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+  for (uint32_t q = q0; q < q1; q++) {
+    Quad m = ~(Quad)0u;
+#pragma unroll
+    for (int t = 0; t < K - 1; t++) m &= pre[t][q];
+    const Quad c0 = m & last[q], c1 = m & last[Q + q], c2 = m & last[2 * Q + q];
+    const Quad yw = (y + (size_t)q * B)[b];
+    n[0] += popc4(c0), n[1] += popc4(c1), n[2] += popc4(c2);
+    a0 += popc4(c0 & yw), a1 += popc4(c1 & yw), a2 += popc4(c2 & yw);
+  }
+}
+
+template <int K, int G>
+__global__ __launch_bounds__(kMdrThreads) void k_mdr_scan_labels(const MdrLabelArgs a) {
+  __shared__ uint32_t s_bits[kMdrLabWaves][64];
+  __shared__ int64_t s_rank[kMdrLabWaves][64];
+  __shared__ uint32_t s_tp[G][kMdrThreads], s_tn[G][kMdrThreads];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int F = a.F, f0 = a.f0, gn = a.gn;
+  const size_t Q = (size_t)a.quads, B = (size_t)a.B;
+  const int64_t bl = (int64_t)a.b0 + (int64_t)blockIdx.y * 64 + lane;
+  const bool live = bl < a.B;
+  // a lane past the last labelling computes the last one's and writes nothing
+  const uint32_t b = (uint32_t)(live ? bl : a.B - 1);
+  const Quad* y = a.y;
+  const int64_t first = a.r0 + (int64_t)blockIdx.x * a.per_block + wave;
+  const int64_t end = min(a.r1, a.r0 + ((int64_t)blockIdx.x + 1) * a.per_block);
+  int cells = 1;
+#pragma unroll
+  for (int t = 1; t < K; t++) cells *= 3;
+
+  uint32_t best_bits[G], best_it[G];
+#pragma unroll
+  for (int i = 0; i < G; i++) best_bits[i] = 0, best_it[i] = kNoIter;
+
+  uint32_t it = 0;
+  int32_t f[K];
+  for (int64_t r = first; r < end; r += kMdrLabWaves, it++) {
+    if (it == 0) mdr_unrank(a.p, K, r, f);
+    else mdr_advance(a.p, K, f, kMdrLabWaves);
+#pragma unroll
+    for (int t = 0; t < K; t++) f[t] = __builtin_amdgcn_readfirstlane(f[t]);
+    uint32_t tp[G], tn[G];
+#pragma unroll
+    for (int i = 0; i < G; i++) tp[i] = tn[i] = 0;
+    PlaneQuad* const planes = (PlaneQuad*)a.planes;
+    PlaneQuad* last = planes + (size_t)f[K - 1] * 3 * Q;
+    for (int cell = 0; cell < cells; cell++) {
+      PlaneQuad* pre[K > 1 ? K - 1 : 1];
+      {
+        int c = cell;
+#pragma unroll
+        for (int t = K - 2; t >= 0; t--) {
+          pre[t] = planes + ((size_t)f[t] * 3 + c % 3) * Q;
+          c /= 3;
+        }
+      }
+      // cn: the cell's count in a fold (uniform); cs: the lane's cases there
+      uint32_t cn[G][3], cs[3][G], totn[3] = {0, 0, 0}, tots[3] = {0, 0, 0};
+      if (gn < F) {  // the other folds' words count towards the totals only
+        count3_labels<K>(pre, last, Q, y, B, b, a.seg_off[0], a.seg_off[f0], totn, tots[0],
+                         tots[1], tots[2]);
+        count3_labels<K>(pre, last, Q, y, B, b, a.seg_off[f0 + gn], a.seg_off[F], totn, tots[0],
+                         tots[1], tots[2]);
+      }
+#pragma unroll
+      for (int i = 0; i < G; i++) {
+#pragma unroll
+        for (int g = 0; g < 3; g++) cn[i][g] = cs[g][i] = 0;
+        if (i < gn) {
+          count3_labels<K>(pre, last, Q, y, B, b, a.seg_off[f0 + i], a.seg_off[f0 + i + 1],
+                           cn[i], cs[0][i], cs[1][i], cs[2][i]);
+#pragma unroll
+          for (int g = 0; g < 3; g++) totn[g] += cn[i][g], tots[g] += cs[g][i];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < G; i++) {
+        if (i < gn) {
+          const uint64_t TC = (a.tc + (size_t)(f0 + i) * B)[b], TN = (a.tn + (size_t)(f0 + i) * B)[b];
+#pragma unroll
+          for (int g = 0; g < 3; g++) {
+            const uint32_t s = tots[g] - (a.sub ? cs[g][i] : 0);
+            const uint32_t c = (totn[g] - tots[g]) - (a.sub ? cn[i][g] - cs[g][i] : 0);
+            const bool high = mdr_high_risk(s, c, TC, TN);
+            tp[i] += high ? s : 0;
+            tn[i] += high ? 0 : c;
+          }
+        }
+      }
+    }
+    // The BAs come out of a loop that stays rolled, through the lane's own
+    // column of LDS.  Unrolled, the float64 divisions by a fold's totals are
+    // loop-invariant in part; the compiler hoists those parts out of the rank
+    // loop for all G folds at once, which costs some 200 registers.
+#pragma unroll
+    for (int i = 0; i < G; i++)
+      if (i < gn) s_tp[i][tid] = tp[i], s_tn[i][tid] = tn[i];
+#pragma unroll 1
+    for (int i = 0; i < gn; i++) {
+      const float ba = mdr_ba(s_tp[i][tid], s_tn[i][tid], (a.tc + (size_t)(f0 + i) * B)[b],
+                              (a.tn + (size_t)(f0 + i) * B)[b]);
+      if (a.ba_out && live) a.ba_out[((size_t)b * F + f0 + i) * (size_t)a.count + r] = ba;
+      s_tp[i][tid] = __float_as_uint(ba);
+    }
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+      if (i < gn) {
+        const uint32_t bits = s_tp[i][tid];
+        // ranks ascend with `it`, so a strict improvement keeps the smallest
+        if (best_it[i] == kNoIter || bits > best_bits[i]) best_bits[i] = bits, best_it[i] = it;
+      }
+    }
+  }
+
+  // per fold: the block's waves hold the same labellings; merge them, then
+  // the block's slot (one block owns it in every launch: no atomics)
+#pragma unroll
+  for (int i = 0; i < G; i++) {
+    if (i < gn) {
+      s_bits[wave][lane] = best_bits[i];
+      s_rank[wave][lane] =
+          best_it[i] == kNoIter ? kMdrNoRank : first + (int64_t)best_it[i] * kMdrLabWaves;
+      __syncthreads();
+      if (tid < 64 && live) {
+        uint32_t bits = s_bits[0][lane];
+        int64_t rank = s_rank[0][lane];
+        for (int w = 1; w < kMdrLabWaves; w++)
+          if (mdr_better(s_bits[w][lane], s_rank[w][lane], bits, rank))
+            bits = s_bits[w][lane], rank = s_rank[w][lane];
+        const size_t slot = ((size_t)blockIdx.x * F + f0 + i) * B + b;
+        if (mdr_better(bits, rank, a.part_bits[slot], a.part_rank[slot]))
+          a.part_bits[slot] = bits, a.part_rank[slot] = rank;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// One thread per (fold, labelling): the best over the blocks' slots.
+__global__ __launch_bounds__(256) void k_mdr_labels_reduce(const uint32_t* __restrict__ part_bits,
+                                                           const int64_t* __restrict__ part_rank,
+                                                           int blocks, int F, int B,
+                                                           uint32_t* __restrict__ out_bits,
+                                                           int64_t* __restrict__ out_rank) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, FB = (size_t)F * B;
+  if (i >= FB) return;
+  uint32_t bits = 0;
+  int64_t rank = kMdrNoRank;
+  for (int x = 0; x < blocks; x++) {
+    const size_t slot = (size_t)x * FB + i;
+    if (mdr_better(part_bits[slot], part_rank[slot], bits, rank))
+      bits = part_bits[slot], rank = part_rank[slot];
+  }
+  const size_t o = (i % B) * F + i / B;  // [labelling][fold]
+  out_bits[o] = bits, out_rank[o] = rank;
+}
+
+template <int K>
+void launch_scan_labels(const MdrLabelArgs& a, dim3 grid, hipStream_t s) {
+  // the usual cv = 5 and cv = 10 get kernels that hold just their folds: the
+  // registers a fold takes decide how many waves a SIMD holds
+  if (a.gn == 1)
+    k_mdr_scan_labels<K, 1><<<grid, kMdrThreads, 0, s>>>(a);
+  else if (a.gn <= 5)
+    k_mdr_scan_labels<K, 5><<<grid, kMdrThreads, 0, s>>>(a);
+  else if (a.gn <= 10)
+    k_mdr_scan_labels<K, 10><<<grid, kMdrThreads, 0, s>>>(a);
+  else
+    k_mdr_scan_labels<K, kMdrG><<<grid, kMdrThreads, 0, s>>>(a);
+}
+
 }  // namespace
 
 int mdr_scan(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int k,
@@ -343,6 +629,184 @@ int mdr_scan(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* 
       memcpy(&best_ba[i], &bits, 4);
       best_rank[i] = rank;
     }
+  if (s) (void)hipStreamDestroy(s);
+  return rc;
+}
+
+namespace {
+thread_local double g_mdr_labels_ms[4] = {-1.0, -1.0, -1.0, -1.0};
+}
+
+void mdr_labels_last_timing(double* ms4) {
+  for (int i = 0; i < 4; i++) ms4[i] = g_mdr_labels_ms[i];
+}
+
+int mdr_scan_labels(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* labels,
+                    int n_labelings, int k, const int32_t* fold, int n_folds, int64_t count,
+                    float* best_ba, int64_t* best_rank, float* ba_out) {
+  if (device_count() <= 0) {
+    set_error("backend='gpu' requested but no HIP device is visible");
+    return FS_ENODEV;
+  }
+  for (double& v : g_mdr_labels_ms) v = -1.0;
+  MdrLayout L;
+  if (int rc = mdr_fold_layout(n, fold, n_folds, 128, L)) return rc;
+  const int F = L.F, B = n_labelings;
+  const int64_t W = L.words * 4;  // L counts quads
+  const size_t FB = (size_t)F * B;
+  std::vector<uint32_t> tc, tn;
+  mdr_label_totals(n, labels, B, L, -1, tc, tn);
+
+  // launches of about 2e11 lane operations each, as in mdr_scan: per
+  // (combination, labelling) the word loop issues 6 per cell and word.  The
+  // labellings go into one launch as far as that allows, then the ranks.
+  int cells = 1;
+  for (int t = 1; t < k; t++) cells *= 3;
+  const int groups = (F + kMdrG - 1) / kMdrG;
+  const double ops = (double)cells * (double)W * 6.0 * (groups > 1 ? 2.0 : 1.0);
+  const double pairs = std::max(2e11 / ops, 64.0 * kMdrLabWaves);
+  const int64_t lab_chunk =
+      std::max<int64_t>(64, std::min<int64_t>((B + 63) / 64 * 64, (int64_t)(pairs / 256.0) / 64 * 64));
+  const int64_t chunk =
+      std::max<int64_t>(kMdrLabWaves, (int64_t)std::min(pairs / (double)lab_chunk, 4e18));
+  // blocks (rank runs) of the largest launch; every launch uses the first ones
+  const int64_t max_bx = std::max<int64_t>(
+      1, std::min<int64_t>(kMdrLabMaxBlocks, (int64_t)(kMdrLabMaxSlots / FB)));
+  const int nbx = (int)std::min<int64_t>(
+      max_bx, (std::min(count, chunk) + kMdrLabWaves - 1) / kMdrLabWaves);
+  const size_t nslots = (size_t)nbx * FB;
+
+  uint8_t *dx = nullptr, *dlab = nullptr;
+  int32_t *dperm = nullptr, *dseg = nullptr;
+  uint32_t *dtc = nullptr, *dtn = nullptr, *dplanes = nullptr, *dy = nullptr, *dpbits = nullptr,
+           *dobits = nullptr;
+  int64_t *dprank = nullptr, *dorank = nullptr;
+  float* dba = nullptr;
+  int* dbad = nullptr;
+  hipStream_t s = nullptr;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  int rc = FS_OK;
+  auto fail = [&](const char* what, hipError_t e) {
+    set_error(std::string("fs_mdr_scan_labels: ") + what + ": " + hipGetErrorString(e));
+    (void)hipGetLastError();
+    rc = (e == hipErrorOutOfMemory) ? FS_EOOM : FS_EHIP;
+  };
+  auto up = [&](void* dst, const void* src, size_t bytes, const char* what) {
+    hipError_t e;
+    if (rc == FS_OK && (e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
+      fail(what, e);
+  };
+  auto mark = [&](int i) {
+    hipError_t e;
+    if (rc == FS_OK && (e = hipEventRecord(ev[i], s)) != hipSuccess) fail("hipEventRecord", e);
+  };
+  hipError_t e;
+  if ((e = hipSetDevice(device)) != hipSuccess) fail("hipSetDevice", e);
+  if (rc == FS_OK && (e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess)
+    fail("hipStreamCreate", e);
+  for (int i = 0; i < 5 && rc == FS_OK; i++)
+    if ((e = hipEventCreate(&ev[i])) != hipSuccess) fail("hipEventCreate", e);
+  DevArena mem(device);  // freed on return, after the stream is synchronised
+  if (rc == FS_OK) rc = mem.alloc(&dx, (size_t)n * p);
+  if (rc == FS_OK) rc = mem.alloc(&dlab, (size_t)B * n);
+  if (rc == FS_OK) rc = mem.alloc(&dperm, L.perm.size());
+  if (rc == FS_OK) rc = mem.alloc(&dseg, L.seg_off.size());
+  if (rc == FS_OK) rc = mem.alloc(&dtc, FB);
+  if (rc == FS_OK) rc = mem.alloc(&dtn, FB);
+  if (rc == FS_OK) rc = mem.alloc(&dplanes, (size_t)W * 3 * (size_t)p);
+  if (rc == FS_OK) rc = mem.alloc(&dy, (size_t)W * B);
+  if (rc == FS_OK) rc = mem.alloc(&dpbits, nslots);
+  if (rc == FS_OK) rc = mem.alloc(&dprank, nslots);
+  if (rc == FS_OK) rc = mem.alloc(&dobits, FB);
+  if (rc == FS_OK) rc = mem.alloc(&dorank, FB);
+  if (rc == FS_OK) rc = mem.alloc(&dbad, 1);
+  if (rc == FS_OK && ba_out) rc = mem.alloc(&dba, FB * (size_t)count);
+  mark(0);
+  up(dx, x, (size_t)n * p, "upload of X");
+  up(dlab, labels, (size_t)B * n, "upload of the labels");
+  up(dperm, L.perm.data(), L.perm.size() * 4, "upload of the sample order");
+  up(dseg, L.seg_off.data(), L.seg_off.size() * 4, "upload of the segments");
+  up(dtc, tc.data(), FB * 4, "upload of the totals");
+  up(dtn, tn.data(), FB * 4, "upload of the totals");
+  if (rc == FS_OK && (e = hipMemsetAsync(dbad, 0, 4, s)) != hipSuccess) fail("hipMemset", e);
+  mark(1);
+
+  if (rc == FS_OK) {
+    // grid.y is limited to 65535: pack the words in slabs
+    const unsigned gx = (unsigned)((p + 255) / 256), gb = (unsigned)((B + 255) / 256);
+    for (int64_t w0 = 0; w0 < W && rc == FS_OK; w0 += 65535) {
+      const int64_t wn = std::min<int64_t>(65535, W - w0);
+      k_mdr_pack_cols<<<dim3(gx, (unsigned)wn), 256, 0, s>>>(dx, p, dperm, W, w0, dplanes, dbad);
+      if ((e = hipGetLastError()) != hipSuccess) fail("pack kernel", e);
+      k_mdr_pack_labels<<<dim3(gb, (unsigned)wn), 256, 0, s>>>(dlab, n, B, dperm, W, w0, dy);
+      if (rc == FS_OK && (e = hipGetLastError()) != hipSuccess) fail("label pack kernel", e);
+    }
+    k_mdr_labels_fill<<<(unsigned)((nslots + 255) / 256), 256, 0, s>>>(dpbits, dprank, nslots);
+    if (rc == FS_OK && (e = hipGetLastError()) != hipSuccess) fail("fill kernel", e);
+  }
+  mark(2);
+  int bad = 0;
+  if (rc == FS_OK && ((e = hipMemcpyAsync(&bad, dbad, 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+                      (e = hipStreamSynchronize(s)) != hipSuccess))
+    fail("pack", e);
+  if (rc == FS_OK && bad) {
+    set_error("fs_mdr_scan_labels: genotypes must be coded 0/1/2");
+    rc = FS_EINVAL;
+  }
+
+  if (rc == FS_OK) {
+    MdrLabelArgs a;
+    a.planes = (const Quad*)dplanes, a.p = p, a.quads = L.words, a.y = (const Quad*)dy, a.seg_off = dseg, a.tc = dtc, a.tn = dtn;
+    a.B = B, a.F = F, a.sub = L.sub, a.count = count, a.ba_out = dba;
+    a.part_bits = dpbits, a.part_rank = dprank;
+    for (int64_t r0 = 0; r0 < count && rc == FS_OK; r0 += chunk) {
+      a.r0 = r0, a.r1 = std::min(count, r0 + chunk);
+      const int64_t runs = (a.r1 - a.r0 + kMdrLabWaves - 1) / kMdrLabWaves;
+      const int blocks = (int)std::min<int64_t>(nbx, runs);
+      a.per_block = (runs + blocks - 1) / blocks * kMdrLabWaves;
+      for (int64_t b0 = 0; b0 < B && rc == FS_OK; b0 += lab_chunk) {
+        a.b0 = (int)b0;
+        const unsigned gy = (unsigned)((std::min<int64_t>(lab_chunk, B - b0) + 63) / 64);
+        for (int f0 = 0; f0 < F && rc == FS_OK; f0 += kMdrG) {
+          a.f0 = f0, a.gn = std::min(kMdrG, F - f0);
+          const dim3 grid((unsigned)blocks, gy);
+          switch (k) {
+            case 1: launch_scan_labels<1>(a, grid, s); break;
+            case 2: launch_scan_labels<2>(a, grid, s); break;
+            case 3: launch_scan_labels<3>(a, grid, s); break;
+            case 4: launch_scan_labels<4>(a, grid, s); break;
+            case 5: launch_scan_labels<5>(a, grid, s); break;
+            default: launch_scan_labels<6>(a, grid, s); break;
+          }
+          if ((e = hipGetLastError()) != hipSuccess) fail("scan kernel", e);
+        }
+      }
+    }
+  }
+  if (rc == FS_OK) {
+    k_mdr_labels_reduce<<<(unsigned)((FB + 255) / 256), 256, 0, s>>>(dpbits, dprank, nbx, F, B,
+                                                                      dobits, dorank);
+    if ((e = hipGetLastError()) != hipSuccess) fail("reduce kernel", e);
+  }
+  mark(3);
+  if (rc == FS_OK &&
+      ((e = hipMemcpyAsync(best_ba, dobits, FB * 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+       (e = hipMemcpyAsync(best_rank, dorank, FB * 8, hipMemcpyDeviceToHost, s)) != hipSuccess))
+    fail("download of the results", e);
+  if (rc == FS_OK && ba_out &&
+      (e = hipMemcpyAsync(ba_out, dba, FB * (size_t)count * 4, hipMemcpyDeviceToHost, s)) !=
+          hipSuccess)
+    fail("download of the balanced accuracies", e);
+  mark(4);
+  if (rc == FS_OK && (e = hipStreamSynchronize(s)) != hipSuccess) fail("scan", e);
+  if (s) (void)hipStreamSynchronize(s);
+  if (rc == FS_OK)
+    for (int i = 0; i < 4; i++) {
+      float ms = -1.0f;
+      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) g_mdr_labels_ms[i] = ms;
+    }
+  for (hipEvent_t v : ev)
+    if (v) (void)hipEventDestroy(v);
   if (s) (void)hipStreamDestroy(s);
   return rc;
 }

@@ -2,6 +2,9 @@
 // and the CPU backend of fs_mdr_scan: the bit-plane / popcount scheme of
 // fs_mdr.h on 64-bit words, the rank range split over host threads.  It
 // replaces _batch_balanced_accuracy_cpu (MDR.py:82-129) for all folds at once.
+// fs_mdr_scan_labels (many labellings of one genotype matrix) follows the
+// same scheme on the fold-only layout: a combination's cell masks are built
+// once and every labelling adds one AND and one popcount per word.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -80,6 +83,96 @@ int mdr_check(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, in
     return FS_EINVAL;
   }
   return FS_OK;
+}
+
+int mdr_fold_layout(int64_t n, const int32_t* fold, int n_folds, int wordbits, MdrLayout& L) {
+  const int F = fold ? n_folds : 1;
+  L.F = F;
+  L.sub = fold ? 1 : 0;
+  L.tc.clear();
+  L.tn.clear();
+  std::vector<int64_t> size((size_t)F, 0);
+  for (int64_t i = 0; i < n; i++) {
+    const int f = fold ? fold[i] : 0;
+    if (f < 0 || f >= F) {
+      set_error("fs_mdr_scan_labels: fold id outside [0, n_folds)");
+      return FS_EINVAL;
+    }
+    size[f]++;
+  }
+  L.seg_off.assign((size_t)F + 1, 0);
+  int64_t w = 0;
+  for (int f = 0; f < F; f++) {
+    L.seg_off[f] = (int32_t)w;
+    w += (size[f] + wordbits - 1) / wordbits;
+  }
+  L.seg_off[F] = (int32_t)w;
+  L.words = w;
+  L.perm.assign((size_t)w * wordbits, -1);
+  std::vector<int64_t> fill((size_t)F);
+  for (int f = 0; f < F; f++) fill[f] = (int64_t)L.seg_off[f] * wordbits;
+  for (int64_t i = 0; i < n; i++) L.perm[fill[fold ? fold[i] : 0]++] = (int32_t)i;
+  return FS_OK;
+}
+
+void mdr_label_totals(int64_t n, const uint8_t* labels, int n_labelings, const MdrLayout& L,
+                      int n_jobs, std::vector<uint32_t>& tc, std::vector<uint32_t>& tn) {
+  const int F = L.F;
+  const size_t B = (size_t)n_labelings;
+  tc.assign((size_t)F * B, 0);
+  tn.assign((size_t)F * B, 0);
+  // the samples in layout order, fold by fold: a fold's cases are one
+  // branch-free sum over its run (random flags would mispredict every second
+  // branch of a test per sample)
+  const int64_t wordbits = L.words ? (int64_t)L.perm.size() / L.words : 0;
+  std::vector<int32_t> order;
+  std::vector<int64_t> start((size_t)F + 1, 0);
+  order.reserve((size_t)n);
+  for (int f = 0; f < F; f++) {
+    for (int64_t pos = L.seg_off[f] * wordbits; pos < L.seg_off[f + 1] * wordbits; pos++)
+      if (L.perm[pos] >= 0) order.push_back(L.perm[pos]);
+    start[f + 1] = (int64_t)order.size();
+  }
+  auto rows = [&](size_t b0, size_t b1) {
+    std::vector<uint32_t> in((size_t)F);
+    for (size_t b = b0; b < b1; b++) {
+      const uint8_t* lab = labels + b * (size_t)n;
+      uint32_t cases = 0;
+      for (int f = 0; f < F; f++) {
+        uint32_t c = 0;
+        for (int64_t j = start[f]; j < start[f + 1]; j++) c += lab[order[j]] != 0;
+        in[f] = c;
+        cases += c;
+      }
+      for (int f = 0; f < F; f++) {
+        const uint32_t size = (uint32_t)(start[f + 1] - start[f]);
+        tc[(size_t)f * B + b] = cases - (L.sub ? in[f] : 0);
+        tn[(size_t)f * B + b] = ((uint32_t)n - cases) - (L.sub ? size - in[f] : 0);
+      }
+    }
+  };
+  // one thread per 2^18 flags, eight at most: the work is a few milliseconds
+  const int nt = (int)std::max<int64_t>(
+      1, std::min<int64_t>({(int64_t)hardware_threads(n_jobs), 8, (int64_t)(B * (size_t)n >> 18),
+                            (int64_t)B}));
+  std::vector<std::thread> th;
+  for (int t = 1; t < nt; t++) th.emplace_back(rows, B * t / nt, B * (t + 1) / nt);
+  rows(0, B / nt);
+  for (auto& t : th) t.join();
+}
+
+int mdr_check_labels(const uint8_t* x, int64_t n, int64_t p, const uint8_t* labels,
+                     int n_labelings, int k, const int32_t* fold, int n_folds,
+                     const float* best_ba, const int64_t* best_rank, int64_t* count) {
+  if (!x || !labels || !best_ba || !best_rank) {
+    set_error("fs_mdr_scan_labels: x, labels, best_ba and best_rank must not be NULL");
+    return FS_EINVAL;
+  }
+  if (n_labelings < 1 || n_labelings > kMdrMaxLabelings) {
+    set_error("fs_mdr_scan_labels: n_labelings must be in 1..65535");
+    return FS_EINVAL;
+  }
+  return mdr_check(x, n, p, labels, k, fold, n_folds, best_ba, best_rank, count);
 }
 
 namespace cpu {
@@ -190,7 +283,172 @@ FS_MDR_POPCNT void scan_one_hw(const uint64_t* planes, int64_t W, const MdrLayou
   scan_one<true>(planes, W, L, k, f, cnt, tp, tn);
 }
 
+// What one thread of the labels scan keeps between combinations.
+struct LabelScratch {
+  std::vector<uint64_t> mask;       // 3 x W: a prefix cell ANDed with the last column
+  std::vector<uint32_t> cell, own;  // 3 x F cell counts; F case counts
+  std::vector<uint32_t> tp, tn;     // B x F
+};
+
+// One combination under every labelling: tp / tn at [b * F + fold].  A prefix
+// cell's three mask rows and their per-fold counts are built once and serve
+// all B labellings; per labelling only popcount(mask & label word) is left.
+template <bool HW>
+__attribute__((always_inline)) inline void scan_labels_one(
+    const uint64_t* planes, int64_t W, const MdrLayout& L, int k, const int32_t* f,
+    const uint64_t* Y, int B, const uint32_t* tc, const uint32_t* tn, LabelScratch& s) {
+  const int F = L.F;
+  int cells = 1;
+  for (int t = 1; t < k; t++) cells *= 3;
+  std::fill(s.tp.begin(), s.tp.end(), 0u);
+  std::fill(s.tn.begin(), s.tn.end(), 0u);
+  const uint64_t* last = planes + (size_t)f[k - 1] * 3 * W;
+  const uint64_t* pre[kMdrMaxK];
+  for (int cell = 0; cell < cells; cell++) {
+    for (int t = k - 2, c = cell; t >= 0; t--, c /= 3)
+      pre[t] = planes + ((size_t)f[t] * 3 + c % 3) * W;
+    uint32_t ctot[3] = {0, 0, 0};
+    for (int g = 0; g < 3; g++)
+      for (int i = 0; i < F; i++) {
+        uint32_t a = 0;
+        for (int64_t w = L.seg_off[i]; w < L.seg_off[i + 1]; w++) {
+          uint64_t m = last[g * W + w];
+          for (int t = 0; t < k - 1; t++) m &= pre[t][w];
+          s.mask[g * W + w] = m;
+          a += (uint32_t)__builtin_popcountll(m);
+        }
+        s.cell[g * F + i] = a;
+        ctot[g] += a;
+      }
+    for (int b = 0; b < B; b++) {
+      const uint64_t* y = Y + (size_t)b * W;
+      for (int g = 0; g < 3; g++) {
+        const uint64_t* m = s.mask.data() + g * W;
+        uint32_t tot = 0;
+        for (int i = 0; i < F; i++) {
+          uint32_t a = 0;
+          for (int64_t w = L.seg_off[i]; w < L.seg_off[i + 1]; w++)
+            a += (uint32_t)__builtin_popcountll(m[w] & y[w]);
+          s.own[i] = a;
+          tot += a;
+        }
+        for (int i = 0; i < F; i++) {
+          const uint32_t cs = tot - (L.sub ? s.own[i] : 0);
+          const uint32_t ct = (ctot[g] - tot) - (L.sub ? s.cell[g * F + i] - s.own[i] : 0);
+          const size_t o = (size_t)i * B + b;
+          if (mdr_high_risk(cs, ct, tc[o], tn[o])) s.tp[(size_t)b * F + i] += cs;
+          else s.tn[(size_t)b * F + i] += ct;
+        }
+      }
+    }
+  }
+}
+
+using LabelScanFn = void (*)(const uint64_t*, int64_t, const MdrLayout&, int, const int32_t*,
+                             const uint64_t*, int, const uint32_t*, const uint32_t*,
+                             LabelScratch&);
+void scan_labels_one_sw(const uint64_t* planes, int64_t W, const MdrLayout& L, int k,
+                        const int32_t* f, const uint64_t* Y, int B, const uint32_t* tc,
+                        const uint32_t* tn, LabelScratch& s) {
+  scan_labels_one<false>(planes, W, L, k, f, Y, B, tc, tn, s);
+}
+FS_MDR_POPCNT void scan_labels_one_hw(const uint64_t* planes, int64_t W, const MdrLayout& L, int k,
+                                      const int32_t* f, const uint64_t* Y, int B,
+                                      const uint32_t* tc, const uint32_t* tn, LabelScratch& s) {
+  scan_labels_one<true>(planes, W, L, k, f, Y, B, tc, tn, s);
+}
+
 }  // namespace
+
+int mdr_scan_labels(const uint8_t* x, int64_t n, int64_t p, const uint8_t* labels,
+                    int n_labelings, int k, const int32_t* fold, int n_folds, int n_jobs,
+                    int64_t count, float* best_ba, int64_t* best_rank, float* ba_out) {
+  MdrLayout L;
+  if (int rc = mdr_fold_layout(n, fold, n_folds, 64, L)) return rc;
+  const int F = L.F, B = n_labelings;
+  const int64_t W = L.words;
+  std::vector<uint64_t> planes, Y;
+  std::vector<uint32_t> tc, tn;
+  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(hardware_threads(n_jobs), count));
+  std::vector<std::vector<Best>> best((size_t)nt);
+  try {
+    if (int rc = pack_planes(x, p, L, n_jobs, planes)) return rc;
+    Y.assign((size_t)B * W, 0);
+    for (int b = 0; b < B; b++) {
+      const uint8_t* lab = labels + (size_t)b * n;
+      for (int64_t w = 0; w < W; w++) {
+        uint64_t bits = 0;
+        for (int i = 0; i < 64; i++) {
+          const int32_t s = L.perm[w * 64 + i];
+          bits |= (uint64_t)(s >= 0 && lab[s >= 0 ? s : 0] != 0) << i;
+        }
+        Y[(size_t)b * W + w] = bits;
+      }
+    }
+    mdr_label_totals(n, labels, B, L, n_jobs, tc, tn);
+    for (auto& v : best) v.assign((size_t)B * F, Best());
+  } catch (const std::bad_alloc&) {
+    set_error("fs_mdr_scan_labels: out of host memory for the bit-planes");
+    return FS_EOOM;
+  }
+  const LabelScanFn scan = have_popcnt() ? scan_labels_one_hw : scan_labels_one_sw;
+  // contiguous rank chunks handed out to the threads; a thread keeps its best
+  // per (labelling, fold), and (BA bits, rank) is a total order, so neither
+  // the hand-out nor the merge order shows in the result
+  const int64_t chunks = std::min<int64_t>(count, (int64_t)nt * 8);
+  std::atomic<int64_t> next{0};
+  std::atomic<int> oom{0};
+  auto work = [&](int me) {
+    LabelScratch s;
+    try {
+      s.mask.resize(3 * (size_t)W);
+      s.cell.resize(3 * (size_t)F);
+      s.own.resize((size_t)F);
+      s.tp.resize((size_t)B * F);
+      s.tn.resize((size_t)B * F);
+    } catch (const std::bad_alloc&) {
+      oom.store(1);
+      return;
+    }
+    int32_t f[kMdrMaxK];
+    Best* mine = best[me].data();
+    for (int64_t c = next++; c < chunks; c = next++) {
+      const int64_t r0 = (int64_t)((__int128)count * c / chunks);
+      const int64_t r1 = (int64_t)((__int128)count * (c + 1) / chunks);
+      if (r0 >= r1) continue;
+      mdr_unrank(p, k, r0, f);
+      for (int64_t r = r0; r < r1; r++) {
+        if (r > r0) mdr_next(p, k, f);
+        scan(planes.data(), W, L, k, f, Y.data(), B, tc.data(), tn.data(), s);
+        for (int b = 0; b < B; b++)
+          for (int i = 0; i < F; i++) {
+            const size_t o = (size_t)b * F + i, t = (size_t)i * B + b;
+            const float ba = mdr_ba(s.tp[o], s.tn[o], tc[t], tn[t]);
+            if (ba_out) ba_out[o * count + r] = ba;
+            uint32_t bits;
+            std::memcpy(&bits, &ba, 4);
+            if (mdr_better(bits, r, mine[o].bits, mine[o].rank)) mine[o].bits = bits, mine[o].rank = r;
+          }
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (int w = 1; w < nt; w++) th.emplace_back(work, w);
+  work(0);
+  for (auto& t : th) t.join();
+  if (oom.load()) {
+    set_error("fs_mdr_scan_labels: out of host memory for a thread's scratch");
+    return FS_EOOM;
+  }
+  for (size_t o = 0; o < (size_t)B * F; o++) {
+    Best m;
+    for (int w = 0; w < nt; w++)
+      if (mdr_better(best[w][o].bits, best[w][o].rank, m.bits, m.rank)) m = best[w][o];
+    std::memcpy(&best_ba[o], &m.bits, 4);
+    best_rank[o] = m.rank;
+  }
+  return FS_OK;
+}
 
 int mdr_scan(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int k,
              const int32_t* fold, int n_folds, int n_jobs, int64_t count, float* best_ba,

@@ -542,6 +542,28 @@ FS_API int fs_plan_destroy(fs_plan* plan);
 FS_API int fs_mdr_scan(int backend, int device, const uint8_t* x, int64_t n, int64_t p,
                        const uint8_t* is_case, int k, const int32_t* fold, int n_folds,
                        int n_jobs, float* best_ba, int64_t* best_rank, float* ba_out);
+/*
+ * fs_mdr_scan for n_labelings phenotype vectors of one genotype matrix in one
+ * pass: the permutation test of an MDR search, or several binary traits.
+ *   labels     [n_labelings][n] row-major, nonzero marks a case; the rows are
+ *              arbitrary (they need not be permutations of each other)
+ *   fold       as in fs_mdr_scan, shared by all labellings
+ *   best_ba    [n_labelings][F], F = max(n_folds, 1)
+ *   best_rank  [n_labelings][F]
+ *   ba_out     NULL, or [n_labelings][F][C(p,k)] float32
+ * Row b of every output holds exactly what fs_mdr_scan(x, labels[b], k, fold,
+ * n_folds) returns, bit for bit, on both backends: the genotype planes are
+ * ANDed once per combination and each labelling adds one AND and one popcount
+ * per word.  FS_EINVAL: as fs_mdr_scan, and n_labelings outside 1..65535.
+ */
+FS_API int fs_mdr_scan_labels(int backend, int device, const uint8_t* x, int64_t n, int64_t p,
+                              const uint8_t* labels, int n_labelings, int k,
+                              const int32_t* fold, int n_folds, int n_jobs, float* best_ba,
+                              int64_t* best_rank, float* ba_out);
+/* Milliseconds the calling thread's last GPU fs_mdr_scan_labels spent on
+ * upload, pack, scan (with the device reduction) and download (HIP events; -1
+ * where unavailable), for the benchmark tool. */
+FS_API int fs_mdr_labels_last_timing(double* ms4);
 /* C(p,k), the length of np.array(list(combinations(range(p), k))) that the
  * reference builds on the host (MDR.py:247-251); FS_EINVAL if above 2^62. */
 FS_API int fs_mdr_combinations(int64_t p, int k, int64_t* count);
