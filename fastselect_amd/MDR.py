@@ -61,6 +61,23 @@ def lookup_table(X, y, interaction):
     return (ratios > threshold).astype(np.uint8)
 
 
+def fold_test_ba(Xc, y, train_idx, test_idx):
+    """Test balanced accuracy of one model in one fold (MDR.py:296-313): the
+    lookup table of the model's columns ``Xc`` on the training rows, applied
+    to the test rows."""
+    own = tuple(range(Xc.shape[1]))
+    lookup = lookup_table(Xc[train_idx], y[train_idx], own)
+    y_test = y[test_idx]
+    y_pred_test = lookup[cell_index(Xc[test_idx], own)]
+    tp = np.sum((y_test == 1) & (y_pred_test == 1))
+    tn = np.sum((y_test == 0) & (y_pred_test == 0))
+    n_pos = np.sum(y_test == 1)
+    n_neg = np.sum(y_test == 0)
+    sens = tp / n_pos if n_pos else 0
+    spec = tn / n_neg if n_neg else 0
+    return (sens + spec) / 2.0
+
+
 def summarise_folds(X, y, splits, best_rank, k, verbose=False):
     """From every fold's best combination rank to the fitted model: the fold's
     lookup table on its training rows, its test balanced accuracy, the
@@ -70,23 +87,12 @@ def summarise_folds(X, y, splits, best_rank, k, verbose=False):
     labelling costs O(folds * n * k).  Returns (best model, its CVC, its mean
     test BA)."""
     n_features = X.shape[1]
-    own = tuple(range(k))
     fold_best_models = []
     fold_test_bas = []
     for fold_i, (train_idx, test_idx) in enumerate(splits):
         best_combo = _lib.mdr_unrank(n_features, k, int(best_rank[fold_i]))
         fold_best_models.append(best_combo)
-        Xc = X[:, best_combo]
-        lookup = lookup_table(Xc[train_idx], y[train_idx], own)
-        y_test = y[test_idx]
-        y_pred_test = lookup[cell_index(Xc[test_idx], own)]
-        tp = np.sum((y_test == 1) & (y_pred_test == 1))
-        tn = np.sum((y_test == 0) & (y_pred_test == 0))
-        n_pos = np.sum(y_test == 1)
-        n_neg = np.sum(y_test == 0)
-        sens = tp / n_pos if n_pos else 0
-        spec = tn / n_neg if n_neg else 0
-        test_ba = (sens + spec) / 2.0
+        test_ba = fold_test_ba(X[:, best_combo], y, train_idx, test_idx)
         fold_test_bas.append(test_ba)
         if verbose:
             print(f"  Fold {fold_i + 1}/{len(splits)}: best {best_combo}, Test BA = {test_ba:.4f}")
@@ -134,6 +140,9 @@ class MDR(ClassifierMixin, BaseEstimator):
 
     ``permutation_test`` fits and adds the permutation null: ``p_value_``,
     ``cvc_p_value_``, ``null_testing_ba_``, ``null_cvc_``, ``n_permutations_``.
+    ``rank_interactions`` fits and adds the ranked list of the search:
+    ``top_interactions_``, ``top_training_ba_``, ``top_mean_testing_ba_``,
+    ``top_cvc_``, ``top_fold_hits_``.
     """
 
     def __init__(self, k: int = 2, cv: int = 10, backend: str = "auto", verbose: bool = False,
@@ -244,6 +253,54 @@ class MDR(ClassifierMixin, BaseEstimator):
         self.n_permutations_ = n_perm
         self.p_value_ = (1 + int(np.sum(null_ba >= self.best_mean_testing_ba_))) / (1 + n_perm)
         self.cvc_p_value_ = (1 + int(np.sum(null_cvc >= self.best_cvc_))) / (1 + n_perm)
+        return self
+
+    def rank_interactions(self, X, y, n_top=100):
+        """``fit`` plus the ranked list of the search: the ``n_top`` best
+        k-way interactions by balanced accuracy on all samples, and how each
+        fares under cross-validation.
+
+        Two ``fs_mdr_scan_top`` calls, one without folds and one with the
+        folds ``fit`` draws; the per-model test accuracies are host numpy,
+        O(m * folds * n * k).  Sets every attribute ``fit`` sets, with the same
+        values, and with m = min(n_top, C(p, k))
+
+        top_interactions_ : ndarray of int, shape (m, k)
+            Ordered by BA on all samples, ties by combination rank.
+        top_training_ba_ : ndarray of float32, shape (m,)
+            That BA (the scan without folds).
+        top_mean_testing_ba_ : ndarray of float64, shape (m,)
+            Mean over all cv folds of the model's test BA, each fold's lookup
+            table built on its training rows.
+        top_cvc_ : ndarray of int, shape (m,)
+            Folds in which the model is that fold's best.
+        top_fold_hits_ : ndarray of int, shape (m,)
+            Folds in which it is among that fold's ``n_top`` best.
+        """
+        n_top = int(n_top)
+        if n_top < 1:
+            raise ValueError(f"n_top must be >= 1. Got {n_top}")
+        if n_top > _lib.MDR_MAX_TOP:
+            raise ValueError(f"n_top must be <= {_lib.MDR_MAX_TOP} (the library's kMdrMaxTop). "
+                             f"Got {n_top}")
+        X, y, k, fold, splits = self._validate(X, y)
+        scan = dict(n_top=n_top, device=self.device, n_jobs=self.n_jobs)
+        all_ba, all_rank = _lib.mdr_scan_top(self.effective_backend_, X, y == 1, k, **scan)
+        _, fold_rank = _lib.mdr_scan_top(self.effective_backend_, X, y == 1, k, fold, len(splits),
+                                         **scan)
+        self._set_model(X, y, *summarise_folds(X, y, splits, fold_rank[:, 0], k, self.verbose))
+
+        m = min(n_top, _lib.mdr_combinations(X.shape[1], k))
+        ranks = all_rank[0, :m]
+        combos = [_lib.mdr_unrank(X.shape[1], k, int(r)) for r in ranks]
+        self.top_interactions_ = np.array(combos, dtype=np.int64).reshape(m, k)
+        self.top_training_ba_ = all_ba[0, :m].copy()
+        self.top_mean_testing_ba_ = np.array(
+            [np.mean([fold_test_ba(X[:, c], y, tr, te) for tr, te in splits]) for c in combos],
+            dtype=np.float64)
+        self.top_cvc_ = np.array([np.sum(fold_rank[:, 0] == r) for r in ranks], dtype=np.int64)
+        self.top_fold_hits_ = np.array([np.sum(np.any(fold_rank == r, axis=1)) for r in ranks],
+                                       dtype=np.int64)
         return self
 
     def predict(self, X):

@@ -8,7 +8,8 @@ scikit-learn surface.  Scoring runs in hand-written HIP kernels for gfx950
 (``fastselect_amd/csrc``) behind the C ABI in ``include/fastselect_amd.h``;
 ``fastselect_amd.parallel`` shards MultiSURF over one process per GPU.
 ``MDR`` is the reference's exhaustive k-way SNP interaction search, the usual
-second stage after a Relief filter; ``mRMR`` (with the
+second stage after a Relief filter (``MDR.rank_interactions``: the ranked list
+of the n_top best interactions, not only the winner); ``mRMR`` (with the
 ``fastselect_amd.mutual_information`` functions it is built on) drops
 redundant features in between, ``CFS`` picks a subset by correlation with
 the class against correlation within the subset, and ``JMI`` (JMI / CMIM) selects

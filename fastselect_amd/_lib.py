@@ -50,7 +50,7 @@ EXPORTED = (
     "fs_surf_score_devices", "fs_set_accumulation", "fs_get_accumulation", "fs_test_hook",
     "fs_multisurf_score_ex", "fs_relieff_score_ex", "fs_surf_score_ex",
     "fs_mdr_scan", "fs_mdr_scan_labels", "fs_mdr_labels_last_timing", "fs_mdr_combinations",
-    "fs_mdr_unrank",
+    "fs_mdr_unrank", "fs_mdr_scan_top", "fs_mdr_top_last_timing",
     "fs_mi_matrices", "fs_mi_last_timing",
     "fs_cfs_create", "fs_cfs_relevance", "fs_cfs_search", "fs_cfs_row", "fs_cfs_search_matrix",
     "fs_cfs_last_timing", "fs_cfs_destroy",
@@ -174,6 +174,11 @@ def _load() -> ctypes.CDLL:
     lib.fs_mdr_scan_labels.restype = _int
     lib.fs_mdr_labels_last_timing.argtypes = [_f64p]
     lib.fs_mdr_labels_last_timing.restype = _int
+    lib.fs_mdr_scan_top.argtypes = [_int, _int, _u8p, _i64, _i64, _u8p, _int, _i32p, _int, _int,
+                                    _int, _f32p, _i64p]
+    lib.fs_mdr_scan_top.restype = _int
+    lib.fs_mdr_top_last_timing.argtypes = [_f64p]
+    lib.fs_mdr_top_last_timing.restype = _int
     lib.fs_mdr_combinations.argtypes = [_i64, _int, _i64p]
     lib.fs_mdr_combinations.restype = _int
     lib.fs_mdr_unrank.argtypes = [_i64, _int, _i64, _i32p]
@@ -848,6 +853,50 @@ def mdr_labels_last_timing():
     ``mdr_scan_labels`` (``fs_mdr_labels_last_timing``; -1 where unavailable)."""
     v = np.full(4, -1.0)
     check(_lib.fs_mdr_labels_last_timing(_p(v, _f64p)))
+    return tuple(float(t) for t in v)
+
+
+MDR_MAX_TOP = 4096  # kMdrMaxTop (fs_mdr.h)
+
+
+def mdr_scan_top(backend, x, is_case, k, fold=None, n_folds=0, n_top=100, device=0, n_jobs=-1):
+    """The ``n_top`` best k-combinations of every fold (``fs_mdr_scan_top``):
+    (top_ba float32[F, n_top], top_rank int64[F, n_top]) with F =
+    max(n_folds, 1), each row ordered by (BA descending, rank ascending) --
+    ``np.argsort(-ba[f], kind="stable")[:n_top]`` of ``mdr_scan``'s ``want_ba``
+    array without that array.  Entries past C(p,k) are rank -1, BA 0; entry 0
+    is ``mdr_scan``'s result.  ``n_top`` is at most ``MDR_MAX_TOP``."""
+    x = np.ascontiguousarray(x, dtype=np.uint8)
+    if x.ndim != 2:
+        raise ValueError("x must be a 2-D array")
+    n, p = x.shape
+    case = np.ascontiguousarray(is_case, dtype=np.uint8)
+    if case.shape != (n,):
+        raise ValueError("is_case must have one entry per row of x")
+    fv = None
+    if fold is not None:
+        fv = np.ascontiguousarray(fold, dtype=np.int32)
+        if fv.shape != (n,):
+            raise ValueError("fold must have one entry per row of x")
+    else:
+        n_folds = 0
+    nf = max(int(n_folds), 1)
+    rows = min(max(int(n_top), 1), MDR_MAX_TOP)  # the call rejects n_top outside this range
+    top_ba = np.zeros((nf, rows), dtype=np.float32)
+    top_rank = np.full((nf, rows), -1, dtype=np.int64)
+    check(_lib.fs_mdr_scan_top(_backend_code(backend), int(device), _p(x, _u8p), n, p,
+                               _p(case, _u8p), int(k), None if fv is None else _p(fv, _i32p),
+                               int(n_folds), int(n_top), int(n_jobs), _p(top_ba, _f32p),
+                               _p(top_rank, _i64p)))
+    return top_ba, top_rank
+
+
+def mdr_top_last_timing():
+    """(upload, pack, scan, download) milliseconds of this thread's last GPU
+    ``mdr_scan_top`` (``fs_mdr_top_last_timing``; -1 where unavailable); the
+    scan phase holds both scans and the selection."""
+    v = np.full(4, -1.0)
+    check(_lib.fs_mdr_top_last_timing(_p(v, _f64p)))
     return tuple(float(t) for t in v)
 
 

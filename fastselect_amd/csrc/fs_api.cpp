@@ -161,6 +161,7 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "cfs_rows_cap") h.cfs_rows_cap = value;
   else if (k == "seg_len") h.seg_len = value;
   else if (k == "pass2_generic") h.pass2_generic = value;
+  else if (k == "mdr_top_cap") h.mdr_top_cap = value;
   else {
     set_error("fs_test_hook: unknown hook '" + k + "'");
     return FS_EINVAL;
@@ -1054,6 +1055,34 @@ int fs_mdr_labels_last_timing(double* ms4) {
     return FS_EINVAL;
   }
   gpu::mdr_labels_last_timing(ms4);
+  return FS_OK;
+}
+
+int fs_mdr_scan_top(int backend, int device, const uint8_t* x, int64_t n, int64_t p,
+                    const uint8_t* is_case, int k, const int32_t* fold, int n_folds, int n_top,
+                    int n_jobs, float* top_ba, int64_t* top_rank) {
+  int rc = check_backend(backend, device);
+  if (rc != FS_OK) return rc;
+  int64_t count = 0;
+  if ((rc = mdr_check(x, n, p, is_case, k, fold, n_folds, top_ba, top_rank, &count)) != FS_OK)
+    return rc;
+  if (n_top < 1 || n_top > kMdrMaxTop) {
+    set_error("fs_mdr_scan_top: n_top must be in 1.." + std::to_string(kMdrMaxTop));
+    return FS_EINVAL;
+  }
+  if (backend == FS_BACKEND_GPU)
+    return gpu::mdr_scan_top(device, x, n, p, is_case, k, fold, n_folds, count, n_top, top_ba,
+                             top_rank);
+  return cpu::mdr_scan_top(x, n, p, is_case, k, fold, n_folds, n_jobs, count, n_top, top_ba,
+                           top_rank);
+}
+
+int fs_mdr_top_last_timing(double* ms4) {
+  if (!ms4) {
+    set_error("fs_mdr_top_last_timing: NULL output");
+    return FS_EINVAL;
+  }
+  gpu::mdr_top_last_timing(ms4);
   return FS_OK;
 }
 

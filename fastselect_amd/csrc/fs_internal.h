@@ -148,6 +148,7 @@ struct TestHooks {
   int64_t cfs_rows_cap = 0;    // >= 1: rows the CFS row cache holds at first (fs_cfs.hip)
   int64_t seg_len = 0;         // >= 1: tiles per pass-2 segment (shard_segments; small n computes 1)
   int64_t pass2_generic = 0;   // 1: every k_score_sparse3 unit takes the plain-HIP walk
+  int64_t mdr_top_cap = 0;     // >= 1: candidates fs_mdr_scan_top's device buffer holds (fs_mdr.hip)
 };
 TestHooks& test_hooks();
 

@@ -162,10 +162,61 @@ int mdr_check_labels(const uint8_t* x, int64_t n, int64_t p, const uint8_t* labe
                      int n_labelings, int k, const int32_t* fold, int n_folds,
                      const float* best_ba, const int64_t* best_rank, int64_t* count);
 
+// fs_mdr_scan_top: the n_top best combinations of every fold under
+// mdr_better's order.  kMdrMaxTop bounds the lists both backends keep (a heap
+// per host thread and fold; on the GPU the candidate buffers hold n_top plus
+// one histogram bin's population); it is a buffer limit, not a measurement.
+constexpr int kMdrMaxTop = 4096;
+
+struct MdrCand {
+  uint32_t bits;
+  int64_t rank;
+};
+inline bool mdr_cand_before(const MdrCand& a, const MdrCand& b) {
+  return mdr_better(a.bits, a.rank, b.bits, b.rank);
+}
+
+// The best `n` candidates pushed so far: a heap with the worst kept on top.
+// (bits, rank) is a total order, so the result does not depend on push order.
+struct MdrTopN {
+  size_t n = 0;
+  std::vector<MdrCand> h;
+  explicit MdrTopN(size_t n_) : n(n_) { h.reserve(n_); }
+  bool full() const { return h.size() >= n; }
+  const MdrCand& worst() const { return h.front(); }
+  void push(MdrCand c);
+  // best first into ba[0..n_top) / rank[0..n_top); unused entries 0 / -1
+  void sorted_into(float* ba, int64_t* rank, int n_top);
+};
+
+// The histogram of the GPU's first scan.  A training BA is 0 or lies in
+// [0.5, 1], so bits >> 14 takes 513 values there: bin 0 holds every BA below
+// 0.5, bin b >= 1 the BAs whose bits >> 14 is kMdrBinBase + b - 1.
+constexpr uint32_t kMdrBinShift = 14;
+constexpr uint32_t kMdrBinBase = 0x3F000000u >> kMdrBinShift;
+constexpr int kMdrBins = (int)((0x3F800000u >> kMdrBinShift) - kMdrBinBase) + 2;
+FS_HD inline uint32_t mdr_bin(uint32_t bits) {
+  const uint32_t h = bits >> kMdrBinShift;
+  if (h < kMdrBinBase) return 0;
+  const uint32_t b = h - kMdrBinBase + 1;
+  return b < (uint32_t)kMdrBins ? b : (uint32_t)kMdrBins - 1;
+}
+// the smallest bit pattern of bin b
+FS_HD inline uint32_t mdr_bin_floor(uint32_t b) {
+  return b == 0 ? 0u : (b - 1 + kMdrBinBase) << kMdrBinShift;
+}
+// The highest bin whose suffix count reaches `need` (1 <= need <= the
+// histogram's total) and that suffix count: the number of BAs at or above
+// the bin's floor.
+void mdr_top_threshold(const uint64_t* hist, uint64_t need, uint32_t* bin, uint64_t* suffix);
+
 namespace cpu {
 int mdr_scan(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int k,
              const int32_t* fold, int n_folds, int n_jobs, int64_t count, float* best_ba,
              int64_t* best_rank, float* ba_out);
+int mdr_scan_top(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int k,
+                 const int32_t* fold, int n_folds, int n_jobs, int64_t count, int n_top,
+                 float* top_ba, int64_t* top_rank);
 int mdr_scan_labels(const uint8_t* x, int64_t n, int64_t p, const uint8_t* labels,
                     int n_labelings, int k, const int32_t* fold, int n_folds, int n_jobs,
                     int64_t count, float* best_ba, int64_t* best_rank, float* ba_out);
@@ -180,6 +231,12 @@ int mdr_scan_labels(int device, const uint8_t* x, int64_t n, int64_t p, const ui
 // Milliseconds of the calling thread's last GPU mdr_scan_labels: upload, pack,
 // scan with the reduction, download (HIP events on the call's stream).
 void mdr_labels_last_timing(double* ms4);
+int mdr_scan_top(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case,
+                 int k, const int32_t* fold, int n_folds, int64_t count, int n_top, float* top_ba,
+                 int64_t* top_rank);
+// The same four phases of the last GPU mdr_scan_top; the scan phase holds both
+// scans, the threshold search between them and the selection.
+void mdr_top_last_timing(double* ms4);
 }
 
 }  // namespace fs

@@ -22,8 +22,14 @@
 //                contiguous run of ranks: a lane unranks once and then steps
 //                its combination by the block size (mdr_advance).
 //
+//                fs_mdr_scan_top runs the same kernel in two more modes (a
+//                histogram of the BAs, then an append of those above a
+//                threshold): see mdr_scan_top below.
+//
 // The GPU backend of fs_mdr_scan_labels (one lane per labelling) follows
 // below, with its own layout and kernels.
+#include <type_traits>
+
 #include "fs_gpu_internal.h"
 #include "fs_mdr.h"
 
@@ -84,7 +90,19 @@ struct MdrScanArgs {
   float* ba_out;            // NULL or F x count
   uint32_t* part_bits;      // kMdrMaxBlocks x F
   int64_t* part_rank;
+  // fs_mdr_scan_top's two scans only
+  unsigned long long* hist = nullptr;  // F x kMdrBins
+  const uint32_t* thr = nullptr;       // F: a candidate of fold f has bits >= thr[f]
+  uint32_t* cursor = nullptr;          // F: candidates of fold f appended so far
+  const uint32_t* cand_off = nullptr;  // F + 1: fold f owns [cand_off[f], cand_off[f + 1])
+  uint32_t* cand_bits = nullptr;
+  int64_t* cand_rank = nullptr;
 };
+
+// What a scan does with a combination's balanced accuracies: keep the best
+// (fs_mdr_scan), count them per histogram bin, or append those at or above a
+// fold's threshold to the fold's candidates (the two scans of fs_mdr_scan_top).
+enum { kScanBest = 0, kScanHist = 1, kScanCollect = 2 };
 
 // popcount(AND) over the words [w0, w1) for the last column's three genotypes
 template <int K>
@@ -102,13 +120,31 @@ __device__ __forceinline__ void count3(const uint32_t* const* pre, const uint32_
   }
 }
 
-template <int K, int G>
+// A read-only table of a launch, as k_mdr_scan reads it in mode MODE.
+template <class T>
+using ConstSpace = const __attribute__((address_space(4))) T;
+template <int MODE, class T>
+using Table = std::conditional_t<MODE == kScanCollect, ConstSpace<T>, const T>;
+
+template <int K, int G, int MODE = kScanBest>
 __global__ __launch_bounds__(kMdrThreads) void k_mdr_scan(const MdrScanArgs a) {
   __shared__ uint32_t s_bits[kMdrThreads / 64];
   __shared__ int64_t s_rank[kMdrThreads / 64];
+  // kScanHist: the block's own histogram, added to the global one at the end
+  // (integer sums: the order of the adds does not show)
+  __shared__ uint32_t s_hist[MODE == kScanHist ? G * kMdrBins : 1];
   const int tid = threadIdx.x;
   const int F = a.F, f0 = a.f0, gn = a.gn;
   const size_t p = (size_t)a.p;
+  // The launch's small tables.  kScanCollect stores inside the rank loop, and
+  // a kernel that stores reads its wave-uniform tables with vector loads
+  // unless they come through the constant address space (as the planes of
+  // k_mdr_scan_labels do); the other modes read them as before.
+  Table<MODE, int32_t>* const seg_off = (Table<MODE, int32_t>*)a.seg_off;
+  Table<MODE, int64_t>* const tot_c = (Table<MODE, int64_t>*)a.tc;
+  Table<MODE, int64_t>* const tot_n = (Table<MODE, int64_t>*)a.tn;
+  [[maybe_unused]] Table<MODE, uint32_t>* const thr = (Table<MODE, uint32_t>*)a.thr;
+  [[maybe_unused]] Table<MODE, uint32_t>* const cand_off = (Table<MODE, uint32_t>*)a.cand_off;
   // the block owns a contiguous run of ranks and takes it 256 at a time
   const int64_t first = a.r0 + (int64_t)blockIdx.x * a.per_block + tid;
   const int64_t end = min(a.r1, a.r0 + ((int64_t)blockIdx.x + 1) * a.per_block);
@@ -119,6 +155,10 @@ __global__ __launch_bounds__(kMdrThreads) void k_mdr_scan(const MdrScanArgs a) {
   uint32_t best_bits[G], best_it[G];
 #pragma unroll
   for (int i = 0; i < G; i++) best_bits[i] = 0, best_it[i] = kNoIter;
+  if constexpr (MODE == kScanHist) {
+    for (int j = tid; j < gn * kMdrBins; j += kMdrThreads) s_hist[j] = 0;
+    __syncthreads();
+  }
 
   uint32_t it = 0;
   int32_t f[K];
@@ -141,10 +181,10 @@ __global__ __launch_bounds__(kMdrThreads) void k_mdr_scan(const MdrScanArgs a) {
       }
       uint32_t cc[3][G], ct[3][G], totc[3] = {0, 0, 0}, totn[3] = {0, 0, 0};
       if (gn < F) {  // the other folds' words count towards the totals only
-        count3<K>(pre, last, p, a.seg_off[0], a.seg_off[f0], totc[0], totc[1], totc[2]);
-        count3<K>(pre, last, p, a.seg_off[f0 + gn], a.seg_off[F], totc[0], totc[1], totc[2]);
-        count3<K>(pre, last, p, a.seg_off[F], a.seg_off[F + f0], totn[0], totn[1], totn[2]);
-        count3<K>(pre, last, p, a.seg_off[F + f0 + gn], a.seg_off[2 * F], totn[0], totn[1],
+        count3<K>(pre, last, p, seg_off[0], seg_off[f0], totc[0], totc[1], totc[2]);
+        count3<K>(pre, last, p, seg_off[f0 + gn], seg_off[F], totc[0], totc[1], totc[2]);
+        count3<K>(pre, last, p, seg_off[F], seg_off[F + f0], totn[0], totn[1], totn[2]);
+        count3<K>(pre, last, p, seg_off[F + f0 + gn], seg_off[2 * F], totn[0], totn[1],
                   totn[2]);
       }
 #pragma unroll
@@ -152,9 +192,9 @@ __global__ __launch_bounds__(kMdrThreads) void k_mdr_scan(const MdrScanArgs a) {
 #pragma unroll
         for (int g = 0; g < 3; g++) cc[g][i] = ct[g][i] = 0;
         if (i < gn) {
-          count3<K>(pre, last, p, a.seg_off[f0 + i], a.seg_off[f0 + i + 1], cc[0][i], cc[1][i],
+          count3<K>(pre, last, p, seg_off[f0 + i], seg_off[f0 + i + 1], cc[0][i], cc[1][i],
                     cc[2][i]);
-          count3<K>(pre, last, p, a.seg_off[F + f0 + i], a.seg_off[F + f0 + i + 1], ct[0][i],
+          count3<K>(pre, last, p, seg_off[F + f0 + i], seg_off[F + f0 + i + 1], ct[0][i],
                     ct[1][i], ct[2][i]);
 #pragma unroll
           for (int g = 0; g < 3; g++) totc[g] += cc[g][i], totn[g] += ct[g][i];
@@ -163,7 +203,7 @@ __global__ __launch_bounds__(kMdrThreads) void k_mdr_scan(const MdrScanArgs a) {
 #pragma unroll
       for (int i = 0; i < G; i++) {
         if (i < gn) {
-          const uint64_t TC = (uint64_t)a.tc[f0 + i], TN = (uint64_t)a.tn[f0 + i];
+          const uint64_t TC = (uint64_t)tot_c[f0 + i], TN = (uint64_t)tot_n[f0 + i];
 #pragma unroll
           for (int g = 0; g < 3; g++) {
             const uint32_t cs = totc[g] - (a.sub ? cc[g][i] : 0);
@@ -175,17 +215,46 @@ __global__ __launch_bounds__(kMdrThreads) void k_mdr_scan(const MdrScanArgs a) {
         }
       }
     }
+    uint32_t hit = 0, hit_bits[MODE == kScanCollect ? G : 1];  // kScanCollect: folds to append to
 #pragma unroll
     for (int i = 0; i < G; i++) {
       if (i < gn) {
-        const float ba = mdr_ba(tp[i], tn[i], (uint64_t)a.tc[f0 + i], (uint64_t)a.tn[f0 + i]);
+        const float ba = mdr_ba(tp[i], tn[i], (uint64_t)tot_c[f0 + i], (uint64_t)tot_n[f0 + i]);
         if (a.ba_out) a.ba_out[(size_t)(f0 + i) * a.count + r] = ba;
         const uint32_t bits = __float_as_uint(ba);
-        // ranks ascend with `it`, so a strict improvement keeps the smallest
-        if (best_it[i] == kNoIter || bits > best_bits[i]) best_bits[i] = bits, best_it[i] = it;
+        if constexpr (MODE == kScanHist) {
+          atomicAdd(&s_hist[i * kMdrBins + mdr_bin(bits)], 1u);  // mdr_bin() < kMdrBins
+        } else if constexpr (MODE == kScanCollect) {
+          hit_bits[i] = bits;
+          hit |= bits >= thr[f0 + i] ? 1u << i : 0u;
+        } else {
+          // ranks ascend with `it`, so a strict improvement keeps the smallest
+          if (best_it[i] == kNoIter || bits > best_bits[i]) best_bits[i] = bits, best_it[i] = it;
+        }
+      }
+    }
+    if constexpr (MODE == kScanCollect) {
+      // rare (about n_top lanes of the whole scan), so one branch for all the
+      // folds keeps it out of the loop's way.  Any append order will do: the
+      // candidates are sorted by a total order afterwards
+      if (hit) {
+#pragma unroll
+        for (int i = 0; i < G; i++) {
+          if (hit & (1u << i)) {
+            const uint32_t o = cand_off[f0 + i], room = cand_off[f0 + i + 1] - o;
+            const uint32_t at = atomicAdd(&a.cursor[f0 + i], 1u);
+            if (at < room) a.cand_bits[o + at] = hit_bits[i], a.cand_rank[o + at] = r;
+          }
+        }
       }
     }
   }
+  if constexpr (MODE == kScanHist) {
+    __syncthreads();
+    for (int j = tid; j < gn * kMdrBins; j += kMdrThreads)
+      if (s_hist[j]) atomicAdd(&a.hist[(size_t)f0 * kMdrBins + j], (unsigned long long)s_hist[j]);
+  }
+  if constexpr (MODE != kScanBest) return;
 
   // per fold: wave reduce, then the block's four waves, then the block's slot
 #pragma unroll
@@ -218,6 +287,27 @@ void launch_scan(const MdrScanArgs& a, int blocks, hipStream_t s) {
     k_mdr_scan<K, 1><<<blocks, kMdrThreads, 0, s>>>(a);
   else
     k_mdr_scan<K, kMdrG><<<blocks, kMdrThreads, 0, s>>>(a);
+}
+
+// The two scans of fs_mdr_scan_top; MODE is kScanHist or kScanCollect.
+template <int K, int MODE>
+void launch_top(const MdrScanArgs& a, int blocks, hipStream_t s) {
+  if (a.F == 1)
+    k_mdr_scan<K, 1, MODE><<<blocks, kMdrThreads, 0, s>>>(a);
+  else
+    k_mdr_scan<K, kMdrG, MODE><<<blocks, kMdrThreads, 0, s>>>(a);
+}
+
+template <int MODE>
+void launch_top_k(int k, const MdrScanArgs& a, int blocks, hipStream_t s) {
+  switch (k) {
+    case 1: launch_top<1, MODE>(a, blocks, s); break;
+    case 2: launch_top<2, MODE>(a, blocks, s); break;
+    case 3: launch_top<3, MODE>(a, blocks, s); break;
+    case 4: launch_top<4, MODE>(a, blocks, s); break;
+    case 5: launch_top<5, MODE>(a, blocks, s); break;
+    default: launch_top<6, MODE>(a, blocks, s); break;
+  }
 }
 
 // ---- fs_mdr_scan_labels: one lane per labelling ---------------------------
@@ -631,6 +721,215 @@ int mdr_scan(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* 
     }
   if (s) (void)hipStreamDestroy(s);
   return rc;
+}
+
+// ---- fs_mdr_scan_top: the n_top best combinations of every fold -----------
+//
+//   Scan A   k_mdr_scan<kScanHist>: per fold a histogram of the BAs' leading
+//            bits (mdr_bin: 514 bins), kept per block in LDS and added to the
+//            global one with integer atomics at the block's end.
+//   Threshold (host, 4 KiB per fold): the highest bin h* whose suffix count
+//            M reaches min(n_top, C(p,k)).  M is the exact number of BAs at
+//            or above the bin's floor, known before any is collected.
+//   Scan B   k_mdr_scan<kScanCollect>: the BAs again; a lane at or above its
+//            fold's floor appends (bits, rank) to the fold's M entries through
+//            an integer cursor.  The host keeps the first n_top under
+//            mdr_better's total order, so the append order does not show.
+//   Ties     When the folds' M together exceed the candidate cap (masses of
+//            equal BAs: monomorphic columns, tiny n, one class), scan B runs
+//            over rank chunks small enough for the cap instead, in ascending
+//            rank order.  The host merges each chunk into the folds' running
+//            lists and raises a full list's threshold to one above its worst
+//            BA: a later rank with an equal BA loses the tie anyway.
+// Device memory: the planes, F x 514 counters and at most max(cap, F)
+// candidates, whatever C(p,k) is.
+namespace {
+constexpr int64_t kMdrTopCap = (int64_t)1 << 20;  // candidates; test hook "mdr_top_cap"
+thread_local double g_mdr_top_ms[4] = {-1.0, -1.0, -1.0, -1.0};
+}  // namespace
+
+void mdr_top_last_timing(double* ms4) {
+  for (int i = 0; i < 4; i++) ms4[i] = g_mdr_top_ms[i];
+}
+
+int mdr_scan_top(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case,
+                 int k, const int32_t* fold, int n_folds, int64_t count, int n_top, float* top_ba,
+                 int64_t* top_rank) {
+  if (device_count() <= 0) return no_device();
+  for (double& v : g_mdr_top_ms) v = -1.0;
+  MdrLayout L;
+  FS_TRY(mdr_layout(n, is_case, fold, n_folds, 32, L));
+  const int F = L.F;
+  const int64_t W = L.words;
+  const uint64_t need = (uint64_t)std::min<int64_t>(n_top, count);
+  const int64_t cap = test_hooks().mdr_top_cap > 0
+                          ? std::min<int64_t>(test_hooks().mdr_top_cap, (int64_t)1 << 30)
+                          : kMdrTopCap;
+  const int64_t chunk_ranks = std::max<int64_t>(1, cap / F);  // of the tie route
+
+  FS_HIP(hipSetDevice(device));
+  DevArena mem(device);
+  StreamLease lease(device);  // destroyed (and the stream synchronised) before `mem`
+  FS_TRY(lease.open(5));
+  hipStream_t s = lease.s;
+  std::vector<hipEvent_t>& ev = lease.ev;
+  uint8_t* dx = nullptr;
+  int32_t *dperm = nullptr, *dseg = nullptr;
+  int64_t *dtc = nullptr, *dtn = nullptr, *dcrank = nullptr;
+  uint32_t *dplanes = nullptr, *dthr = nullptr, *dcursor = nullptr, *doff = nullptr,
+           *dcbits = nullptr;
+  unsigned long long* dhist = nullptr;
+  int* dbad = nullptr;
+  const size_t nhist = (size_t)F * kMdrBins;
+  FS_TRY(mem.alloc(&dx, (size_t)n * p));
+  FS_TRY(mem.alloc(&dperm, L.perm.size()));
+  FS_TRY(mem.alloc(&dseg, L.seg_off.size()));
+  FS_TRY(mem.alloc(&dtc, (size_t)F));
+  FS_TRY(mem.alloc(&dtn, (size_t)F));
+  FS_TRY(mem.alloc(&dplanes, (size_t)W * 3 * (size_t)p));
+  FS_TRY(mem.alloc(&dhist, nhist));
+  FS_TRY(mem.alloc(&dthr, (size_t)F));
+  FS_TRY(mem.alloc(&dcursor, (size_t)F));
+  FS_TRY(mem.alloc(&doff, (size_t)F + 1));
+  FS_TRY(mem.alloc(&dbad, 1));
+
+  FS_HIP(hipEventRecord(ev[0], s));
+  FS_HIP(hipMemcpyAsync(dx, x, (size_t)n * p, hipMemcpyHostToDevice, s));
+  FS_HIP(hipMemcpyAsync(dperm, L.perm.data(), L.perm.size() * 4, hipMemcpyHostToDevice, s));
+  FS_HIP(hipMemcpyAsync(dseg, L.seg_off.data(), L.seg_off.size() * 4, hipMemcpyHostToDevice, s));
+  FS_HIP(hipMemcpyAsync(dtc, L.tc.data(), (size_t)F * 8, hipMemcpyHostToDevice, s));
+  FS_HIP(hipMemcpyAsync(dtn, L.tn.data(), (size_t)F * 8, hipMemcpyHostToDevice, s));
+  FS_HIP(hipMemsetAsync(dbad, 0, 4, s));
+  FS_HIP(hipMemsetAsync(dhist, 0, nhist * 8, s));
+  FS_HIP(hipEventRecord(ev[1], s));
+  {
+    // grid.y is limited to 65535: pack the words in slabs
+    const unsigned gx = (unsigned)((p + 255) / 256);
+    for (int64_t w0 = 0; w0 < W; w0 += 65535) {
+      const int64_t wn = std::min<int64_t>(65535, W - w0);
+      k_mdr_pack<<<dim3(gx, (unsigned)wn), 256, 0, s>>>(dx, p, dperm + w0 * 32, wn,
+                                                        dplanes + (size_t)w0 * 3 * p, dbad);
+      FS_TRY(launch_check("k_mdr_pack"));
+    }
+  }
+  FS_HIP(hipEventRecord(ev[2], s));
+  int bad = 0;
+  FS_HIP(hipMemcpyAsync(&bad, dbad, 4, hipMemcpyDeviceToHost, s));
+  FS_HIP(hipStreamSynchronize(s));
+  if (bad) {
+    set_error("fs_mdr_scan_top: genotypes must be coded 0/1/2");
+    return FS_EINVAL;
+  }
+
+  MdrScanArgs a;
+  a.planes = dplanes, a.p = p, a.seg_off = dseg, a.tc = dtc, a.tn = dtn;
+  a.F = F, a.sub = L.sub, a.count = count, a.ba_out = nullptr;
+  a.part_bits = nullptr, a.part_rank = nullptr;
+  a.hist = dhist, a.thr = dthr, a.cursor = dcursor, a.cand_off = doff;
+  // one scan of the ranks [r0, r1), every fold group
+  auto scan = [&](int mode, int64_t r0, int64_t r1) -> int {
+    a.r0 = r0, a.r1 = r1;
+    const int blocks =
+        (int)std::min<int64_t>(kMdrMaxBlocks, (r1 - r0 + kMdrThreads - 1) / kMdrThreads);
+    const int64_t iters =
+        (r1 - r0 + (int64_t)blocks * kMdrThreads - 1) / ((int64_t)blocks * kMdrThreads);
+    a.per_block = iters * kMdrThreads;
+    for (int f0 = 0; f0 < F; f0 += kMdrG) {
+      a.f0 = f0, a.gn = std::min(kMdrG, F - f0);
+      if (mode == kScanHist) launch_top_k<kScanHist>(k, a, blocks, s);
+      else launch_top_k<kScanCollect>(k, a, blocks, s);
+      FS_TRY(launch_check("k_mdr_scan"));
+    }
+    return FS_OK;
+  };
+  // launches of about 2e11 lane operations each, as in mdr_scan
+  int cells = 1;
+  for (int t = 1; t < k; t++) cells *= 3;
+  const int groups = (F + kMdrG - 1) / kMdrG;
+  const double ops = (double)cells * (double)W * (k + 5) * (groups > 1 ? 2.0 : 1.0);
+  const int64_t chunk = (int64_t)std::max(65536.0, std::min(2e11 / ops, 4e18));
+
+  for (int64_t r0 = 0; r0 < count; r0 += chunk)
+    FS_TRY(scan(kScanHist, r0, std::min(count, r0 + chunk)));
+  std::vector<uint64_t> hist(nhist);
+  FS_HIP(hipMemcpyAsync(hist.data(), dhist, nhist * 8, hipMemcpyDeviceToHost, s));
+  FS_HIP(hipStreamSynchronize(s));
+  std::vector<uint32_t> thr((size_t)F), off((size_t)F + 1, 0), cursor((size_t)F);
+  uint64_t total = 0;
+  for (int i = 0; i < F; i++) {
+    uint32_t bin;
+    uint64_t m;
+    mdr_top_threshold(&hist[(size_t)i * kMdrBins], need, &bin, &m);
+    if (m < need) {
+      set_error("fs_mdr_scan_top: the histogram holds fewer balanced accuracies than combinations");
+      return FS_EHIP;
+    }
+    thr[i] = mdr_bin_floor(bin);
+    total += m;
+    off[i + 1] = (uint32_t)std::min<uint64_t>(total, UINT32_MAX);
+  }
+  const bool ties = total > (uint64_t)cap;
+  if (ties)
+    for (int i = 0; i <= F; i++) off[i] = (uint32_t)(i * chunk_ranks);
+  const size_t ncand = off[F];
+  FS_TRY(mem.alloc(&dcbits, ncand));
+  FS_TRY(mem.alloc(&dcrank, ncand));
+  a.cand_bits = dcbits, a.cand_rank = dcrank;
+  FS_HIP(hipMemcpyAsync(doff, off.data(), ((size_t)F + 1) * 4, hipMemcpyHostToDevice, s));
+
+  std::vector<MdrTopN> top;
+  for (int i = 0; i < F; i++) top.emplace_back((size_t)need);
+  std::vector<uint32_t> cbits(ncand);
+  std::vector<int64_t> crank(ncand);
+  // ranks [r0, r1): collect, then merge the folds' candidates into `top`
+  auto collect = [&](int64_t r0, int64_t r1, bool last) -> int {
+    FS_HIP(hipMemcpyAsync(dthr, thr.data(), (size_t)F * 4, hipMemcpyHostToDevice, s));
+    FS_HIP(hipMemsetAsync(dcursor, 0, (size_t)F * 4, s));
+    for (int64_t q0 = r0; q0 < r1; q0 += chunk)
+      FS_TRY(scan(kScanCollect, q0, std::min(r1, q0 + chunk)));
+    if (last) FS_HIP(hipEventRecord(ev[3], s));
+    FS_HIP(hipMemcpyAsync(cursor.data(), dcursor, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+    if (ties) {  // the folds' counts first: a chunk leaves most buffers empty
+      FS_HIP(hipStreamSynchronize(s));
+      for (int i = 0; i < F; i++) {
+        const size_t m = std::min<size_t>(cursor[i], off[i + 1] - off[i]);
+        if (m == 0) continue;
+        FS_HIP(hipMemcpyAsync(&cbits[off[i]], dcbits + off[i], m * 4, hipMemcpyDeviceToHost, s));
+        FS_HIP(hipMemcpyAsync(&crank[off[i]], dcrank + off[i], m * 8, hipMemcpyDeviceToHost, s));
+      }
+    } else if (ncand) {  // every buffer is full: its size is the histogram's count
+      FS_HIP(hipMemcpyAsync(cbits.data(), dcbits, ncand * 4, hipMemcpyDeviceToHost, s));
+      FS_HIP(hipMemcpyAsync(crank.data(), dcrank, ncand * 8, hipMemcpyDeviceToHost, s));
+    }
+    FS_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < F; i++) {
+      const size_t m = cursor[i], room = off[i + 1] - off[i];
+      if (m > room || (!ties && m != room)) {
+        set_error("fs_mdr_scan_top: the two scans disagree on the number of candidates");
+        return FS_EHIP;
+      }
+      for (size_t j = off[i]; j < off[i] + m; j++) top[i].push({cbits[j], crank[j]});
+      // later ranks lose a tie with the list's worst: only larger BAs count
+      if (top[i].full()) thr[i] = std::max(thr[i], top[i].worst().bits + 1);
+    }
+    return FS_OK;
+  };
+  if (!ties) {
+    FS_TRY(collect(0, count, true));
+  } else {
+    for (int64_t r0 = 0; r0 < count; r0 += chunk_ranks)
+      FS_TRY(collect(r0, std::min(count, r0 + chunk_ranks), r0 + chunk_ranks >= count));
+  }
+  FS_HIP(hipEventRecord(ev[4], s));
+  FS_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < F; i++)
+    top[i].sorted_into(top_ba + (size_t)i * n_top, top_rank + (size_t)i * n_top, n_top);
+  for (int i = 0; i < 4; i++) {
+    float ms = -1.0f;
+    if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) g_mdr_top_ms[i] = ms;
+  }
+  (void)hipGetLastError();
+  return FS_OK;
 }
 
 namespace {

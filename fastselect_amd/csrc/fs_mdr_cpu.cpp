@@ -5,6 +5,9 @@
 // fs_mdr_scan_labels (many labellings of one genotype matrix) follows the
 // same scheme on the fold-only layout: a combination's cell masks are built
 // once and every labelling adds one AND and one popcount per word.
+// fs_mdr_scan_top runs fs_mdr_scan's loop and keeps a bounded heap of the
+// n_top best (BA bits, rank) per thread and fold, merged at the end; the heap
+// and the histogram threshold search of the GPU backend live here too.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -83,6 +86,35 @@ int mdr_check(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, in
     return FS_EINVAL;
   }
   return FS_OK;
+}
+
+void MdrTopN::push(MdrCand c) {
+  if (h.size() < n) {
+    h.push_back(c);
+    std::push_heap(h.begin(), h.end(), mdr_cand_before);
+  } else if (n > 0 && mdr_cand_before(c, h.front())) {
+    std::pop_heap(h.begin(), h.end(), mdr_cand_before);
+    h.back() = c;
+    std::push_heap(h.begin(), h.end(), mdr_cand_before);
+  }
+}
+
+void MdrTopN::sorted_into(float* ba, int64_t* rank, int n_top) {
+  std::sort_heap(h.begin(), h.end(), mdr_cand_before);  // ascending: the best first
+  for (int j = 0; j < n_top; j++) {
+    const bool have = (size_t)j < h.size();
+    const uint32_t bits = have ? h[j].bits : 0u;
+    std::memcpy(&ba[j], &bits, 4);
+    rank[j] = have ? h[j].rank : -1;
+  }
+}
+
+void mdr_top_threshold(const uint64_t* hist, uint64_t need, uint32_t* bin, uint64_t* suffix) {
+  uint64_t sum = 0;
+  int b = kMdrBins;
+  while (b > 0 && sum < need) sum += hist[--b];
+  *bin = (uint32_t)b;
+  *suffix = sum;
 }
 
 int mdr_fold_layout(int64_t n, const int32_t* fold, int n_folds, int wordbits, MdrLayout& L) {
@@ -450,6 +482,47 @@ int mdr_scan_labels(const uint8_t* x, int64_t n, int64_t p, const uint8_t* label
   return FS_OK;
 }
 
+namespace {
+
+// The scan both fs_mdr_scan and fs_mdr_scan_top run: contiguous rank chunks,
+// several per thread, handed out to nt threads; visit(thread, chunk, rank,
+// fold, ba, bits) sees every balanced accuracy, a chunk's in rank order.
+template <class Visit>
+void scan_chunks(const std::vector<uint64_t>& planes, const MdrLayout& L, int64_t p, int k,
+                 int64_t count, int nt, int64_t chunks, Visit visit) {
+  const int F = L.F;
+  const int64_t W = L.words;
+  const ScanFn scan = have_popcnt() ? scan_one_hw : scan_one_sw;
+  std::atomic<int64_t> next{0};
+  auto work = [&](int me) {
+    std::vector<uint32_t> cnt(6 * (size_t)F);
+    std::vector<uint64_t> tp(F), tn(F);
+    int32_t f[kMdrMaxK];
+    for (int64_t c = next++; c < chunks; c = next++) {
+      const int64_t r0 = (int64_t)((__int128)count * c / chunks);
+      const int64_t r1 = (int64_t)((__int128)count * (c + 1) / chunks);
+      if (r0 >= r1) continue;
+      mdr_unrank(p, k, r0, f);
+      for (int64_t r = r0; r < r1; r++) {
+        if (r > r0) mdr_next(p, k, f);
+        scan(planes.data(), W, L, k, f, cnt.data(), tp.data(), tn.data());
+        for (int i = 0; i < F; i++) {
+          const float ba = mdr_ba(tp[i], tn[i], (uint64_t)L.tc[i], (uint64_t)L.tn[i]);
+          uint32_t bits;
+          std::memcpy(&bits, &ba, 4);
+          visit(me, c, r, i, ba, bits);
+        }
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (int w = 1; w < nt; w++) th.emplace_back(work, w);
+  work(0);
+  for (auto& t : th) t.join();
+}
+
+}  // namespace
+
 int mdr_scan(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int k,
              const int32_t* fold, int n_folds, int n_jobs, int64_t count, float* best_ba,
              int64_t* best_rank, float* ba_out) {
@@ -463,41 +536,17 @@ int mdr_scan(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int
     return FS_EOOM;
   }
   const int F = L.F;
-  const int64_t W = L.words;
-  const ScanFn scan = have_popcnt() ? scan_one_hw : scan_one_sw;
-  // contiguous rank chunks, several per thread; each keeps its own best, and
-  // the chunks merge in rank order (the result does not depend on threads)
+  // each chunk keeps its own best, and the chunks merge in rank order (the
+  // result does not depend on threads)
   const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(hardware_threads(n_jobs), count));
   const int64_t chunks = std::min<int64_t>(count, (int64_t)nt * 8);
   std::vector<Best> best((size_t)chunks * F);
-  std::atomic<int64_t> next{0};
-  auto work = [&]() {
-    std::vector<uint32_t> cnt(6 * (size_t)F);
-    std::vector<uint64_t> tp(F), tn(F);
-    int32_t f[kMdrMaxK];
-    for (int64_t c = next++; c < chunks; c = next++) {
-      const int64_t r0 = (int64_t)((__int128)count * c / chunks);
-      const int64_t r1 = (int64_t)((__int128)count * (c + 1) / chunks);
-      if (r0 >= r1) continue;
-      mdr_unrank(p, k, r0, f);
-      Best* b = &best[(size_t)c * F];
-      for (int64_t r = r0; r < r1; r++) {
-        if (r > r0) mdr_next(p, k, f);
-        scan(planes.data(), W, L, k, f, cnt.data(), tp.data(), tn.data());
-        for (int i = 0; i < F; i++) {
-          const float ba = mdr_ba(tp[i], tn[i], (uint64_t)L.tc[i], (uint64_t)L.tn[i]);
-          if (ba_out) ba_out[(size_t)i * count + r] = ba;
-          uint32_t bits;
-          std::memcpy(&bits, &ba, 4);
-          if (mdr_better(bits, r, b[i].bits, b[i].rank)) b[i].bits = bits, b[i].rank = r;
-        }
-      }
-    }
-  };
-  std::vector<std::thread> th;
-  for (int w = 1; w < nt; w++) th.emplace_back(work);
-  work();
-  for (auto& t : th) t.join();
+  scan_chunks(planes, L, p, k, count, nt, chunks,
+              [&](int, int64_t c, int64_t r, int i, float ba, uint32_t bits) {
+                if (ba_out) ba_out[(size_t)i * count + r] = ba;
+                Best& b = best[(size_t)c * F + i];
+                if (mdr_better(bits, r, b.bits, b.rank)) b.bits = bits, b.rank = r;
+              });
   for (int i = 0; i < F; i++) {
     Best m;
     for (int64_t c = 0; c < chunks; c++) {
@@ -506,6 +555,37 @@ int mdr_scan(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int
     }
     std::memcpy(&best_ba[i], &m.bits, 4);
     best_rank[i] = m.rank;
+  }
+  return FS_OK;
+}
+
+int mdr_scan_top(const uint8_t* x, int64_t n, int64_t p, const uint8_t* is_case, int k,
+                 const int32_t* fold, int n_folds, int n_jobs, int64_t count, int n_top,
+                 float* top_ba, int64_t* top_rank) {
+  MdrLayout L;
+  if (int rc = mdr_layout(n, is_case, fold, n_folds, 64, L)) return rc;
+  std::vector<uint64_t> planes;
+  const int F = L.F;
+  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(hardware_threads(n_jobs), count));
+  const size_t keep = (size_t)std::min<int64_t>(n_top, count);
+  // a bounded heap per (thread, fold); merged at the end
+  std::vector<MdrTopN> heap;
+  try {
+    if (int rc = pack_planes(x, p, L, n_jobs, planes)) return rc;
+    for (size_t i = 0; i < (size_t)nt * F; i++) heap.emplace_back(keep);
+  } catch (const std::bad_alloc&) {
+    set_error("fs_mdr_scan_top: out of host memory for the genotype planes");
+    return FS_EOOM;
+  }
+  scan_chunks(planes, L, p, k, count, nt, std::min<int64_t>(count, (int64_t)nt * 8),
+              [&](int me, int64_t, int64_t r, int i, float, uint32_t bits) {
+                heap[(size_t)me * F + i].push({bits, r});
+              });
+  for (int i = 0; i < F; i++) {
+    MdrTopN& m = heap[i];
+    for (int w = 1; w < nt; w++)
+      for (const MdrCand& c : heap[(size_t)w * F + i].h) m.push(c);
+    m.sorted_into(top_ba + (size_t)i * n_top, top_rank + (size_t)i * n_top, n_top);
   }
   return FS_OK;
 }

@@ -564,6 +564,30 @@ FS_API int fs_mdr_scan_labels(int backend, int device, const uint8_t* x, int64_t
  * upload, pack, scan (with the device reduction) and download (HIP events; -1
  * where unavailable), for the benchmark tool. */
 FS_API int fs_mdr_labels_last_timing(double* ms4);
+/*
+ * The n_top best combinations of every fold instead of the one best: the
+ * ranked list ("model landscape") of an MDR search, without the F x C(p,k)
+ * array of ba_out.  Arguments and checks as fs_mdr_scan, and
+ *   n_top      1..4096 (kMdrMaxTop, the size the backends' buffers are laid
+ *              out for)
+ *   top_ba     [F][n_top] float32, F = max(n_folds, 1)
+ *   top_rank   [F][n_top]
+ * Row f holds the first min(n_top, C(p,k)) combinations of fold f ordered by
+ * (float32 BA descending, rank ascending), i.e. np.argsort(-ba_out[f],
+ * kind="stable")[:n_top] and the BAs there; entries past C(p,k) are rank -1,
+ * BA 0.  Entry 0 of a row is what fs_mdr_scan returns for that fold.  Both
+ * backends give the same bits, whatever the thread count or launch schedule.
+ * The GPU backend scans twice (a histogram of the BAs' leading bits, then the
+ * combinations at or above the bin that holds the n_top-th); its device
+ * memory does not grow with C(p,k).  FS_EINVAL: as fs_mdr_scan, n_top out of
+ * range, NULL outputs.
+ */
+FS_API int fs_mdr_scan_top(int backend, int device, const uint8_t* x, int64_t n, int64_t p,
+                           const uint8_t* is_case, int k, const int32_t* fold, int n_folds,
+                           int n_top, int n_jobs, float* top_ba, int64_t* top_rank);
+/* As fs_mdr_labels_last_timing for the last GPU fs_mdr_scan_top: upload, pack,
+ * scan (both scans, the threshold search and the selection), download. */
+FS_API int fs_mdr_top_last_timing(double* ms4);
 /* C(p,k), the length of np.array(list(combinations(range(p), k))) that the
  * reference builds on the host (MDR.py:247-251); FS_EINVAL if above 2^62. */
 FS_API int fs_mdr_combinations(int64_t p, int k, int64_t* count);
