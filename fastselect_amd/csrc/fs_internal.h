@@ -149,6 +149,9 @@ struct TestHooks {
   int64_t seg_len = 0;         // >= 1: tiles per pass-2 segment (shard_segments; small n computes 1)
   int64_t pass2_generic = 0;   // 1: every k_score_sparse3 unit takes the plain-HIP walk
   int64_t mdr_top_cap = 0;     // >= 1: candidates fs_mdr_scan_top's device buffer holds (fs_mdr.hip)
+  int64_t mdr_ranks = 0;       // >= 1: ranks per launch of the three MDR scans, no 65536 floor (fs_mdr.hip)
+  int64_t mdr_blocks = 0;      // >= 1: blocks (rank runs) per launch of the three MDR scans at most
+  int64_t mdr_labels = 0;      // >= 64: labellings per launch of fs_mdr_scan_labels, taken down to a multiple of 64
 };
 TestHooks& test_hooks();
 

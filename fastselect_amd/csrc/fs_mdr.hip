@@ -43,6 +43,18 @@ constexpr int kMdrThreads = 256;
 constexpr int kMdrMaxBlocks = 2048;
 constexpr uint32_t kNoIter = 0xffffffffu;
 
+// Launch sizes.  The test hooks "mdr_ranks" and "mdr_blocks" shrink them so
+// that a small search takes several launches and a block several steps of
+// mdr_advance; at 0 the arguments come back as they are.
+inline int64_t launch_ranks(int64_t computed) {
+  const int64_t h = test_hooks().mdr_ranks;
+  return h > 0 ? h : computed;
+}
+inline int64_t launch_blocks(int64_t cap) {
+  const int64_t h = test_hooks().mdr_blocks;
+  return h > 0 ? std::min(h, cap) : cap;
+}
+
 // The 32 samples at perm[0..32) of column j -> the column's three genotype
 // words; true when a genotype is above 2.
 __device__ __forceinline__ bool pack_word(const uint8_t* __restrict__ x, int64_t p,
@@ -669,7 +681,7 @@ int mdr_scan(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* 
     for (int t = 1; t < k; t++) cells *= 3;
     const int groups = (F + kMdrG - 1) / kMdrG;
     const double ops = (double)cells * (double)W * (k + 5) * (groups > 1 ? 2.0 : 1.0);
-    int64_t chunk = (int64_t)std::max(65536.0, std::min(2e11 / ops, 4e18));
+    const int64_t chunk = launch_ranks((int64_t)std::max(65536.0, std::min(2e11 / ops, 4e18)));
     MdrScanArgs a;
     a.planes = dplanes, a.p = p, a.seg_off = dseg, a.tc = dtc, a.tn = dtn;
     a.F = F, a.sub = L.sub, a.count = count, a.ba_out = dba;
@@ -677,7 +689,7 @@ int mdr_scan(int device, const uint8_t* x, int64_t n, int64_t p, const uint8_t* 
     for (int64_t r0 = 0; r0 < count && rc == FS_OK; r0 += chunk) {
       a.r0 = r0, a.r1 = std::min(count, r0 + chunk);
       const int blocks = (int)std::min<int64_t>(
-          kMdrMaxBlocks, (a.r1 - a.r0 + kMdrThreads - 1) / kMdrThreads);
+          launch_blocks(kMdrMaxBlocks), (a.r1 - a.r0 + kMdrThreads - 1) / kMdrThreads);
       const int64_t iters = (a.r1 - a.r0 + (int64_t)blocks * kMdrThreads - 1) /
                             ((int64_t)blocks * kMdrThreads);
       a.per_block = iters * kMdrThreads;
@@ -829,8 +841,8 @@ int mdr_scan_top(int device, const uint8_t* x, int64_t n, int64_t p, const uint8
   // one scan of the ranks [r0, r1), every fold group
   auto scan = [&](int mode, int64_t r0, int64_t r1) -> int {
     a.r0 = r0, a.r1 = r1;
-    const int blocks =
-        (int)std::min<int64_t>(kMdrMaxBlocks, (r1 - r0 + kMdrThreads - 1) / kMdrThreads);
+    const int blocks = (int)std::min<int64_t>(launch_blocks(kMdrMaxBlocks),
+                                              (r1 - r0 + kMdrThreads - 1) / kMdrThreads);
     const int64_t iters =
         (r1 - r0 + (int64_t)blocks * kMdrThreads - 1) / ((int64_t)blocks * kMdrThreads);
     a.per_block = iters * kMdrThreads;
@@ -847,7 +859,7 @@ int mdr_scan_top(int device, const uint8_t* x, int64_t n, int64_t p, const uint8
   for (int t = 1; t < k; t++) cells *= 3;
   const int groups = (F + kMdrG - 1) / kMdrG;
   const double ops = (double)cells * (double)W * (k + 5) * (groups > 1 ? 2.0 : 1.0);
-  const int64_t chunk = (int64_t)std::max(65536.0, std::min(2e11 / ops, 4e18));
+  const int64_t chunk = launch_ranks((int64_t)std::max(65536.0, std::min(2e11 / ops, 4e18)));
 
   for (int64_t r0 = 0; r0 < count; r0 += chunk)
     FS_TRY(scan(kScanHist, r0, std::min(count, r0 + chunk)));
@@ -964,13 +976,17 @@ int mdr_scan_labels(int device, const uint8_t* x, int64_t n, int64_t p, const ui
   const int groups = (F + kMdrG - 1) / kMdrG;
   const double ops = (double)cells * (double)W * 6.0 * (groups > 1 ? 2.0 : 1.0);
   const double pairs = std::max(2e11 / ops, 64.0 * kMdrLabWaves);
+  // test hook "mdr_labels": labellings per launch
   const int64_t lab_chunk =
-      std::max<int64_t>(64, std::min<int64_t>((B + 63) / 64 * 64, (int64_t)(pairs / 256.0) / 64 * 64));
-  const int64_t chunk =
-      std::max<int64_t>(kMdrLabWaves, (int64_t)std::min(pairs / (double)lab_chunk, 4e18));
+      test_hooks().mdr_labels > 0
+          ? std::max<int64_t>(64, test_hooks().mdr_labels / 64 * 64)
+          : std::max<int64_t>(64, std::min<int64_t>((B + 63) / 64 * 64,
+                                                    (int64_t)(pairs / 256.0) / 64 * 64));
+  const int64_t chunk = launch_ranks(
+      std::max<int64_t>(kMdrLabWaves, (int64_t)std::min(pairs / (double)lab_chunk, 4e18)));
   // blocks (rank runs) of the largest launch; every launch uses the first ones
   const int64_t max_bx = std::max<int64_t>(
-      1, std::min<int64_t>(kMdrLabMaxBlocks, (int64_t)(kMdrLabMaxSlots / FB)));
+      1, std::min<int64_t>(launch_blocks(kMdrLabMaxBlocks), (int64_t)(kMdrLabMaxSlots / FB)));
   const int nbx = (int)std::min<int64_t>(
       max_bx, (std::min(count, chunk) + kMdrLabWaves - 1) / kMdrLabWaves);
   const size_t nslots = (size_t)nbx * FB;

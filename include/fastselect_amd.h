@@ -117,8 +117,9 @@ FS_API int fs_get_accumulation(void);
  * "exact_gather", "row_panel",
  * "rf_xlds", "rf_fcap", "ties_1w", "ties_coop", "rf_ref_replay", "ref_q16", "surf_f64",
  * "colsort_bins12", "colsort_global", "star_split", "colsort_star", "mi_tiles",
- * "list_cap").  FS_EINVAL for an unknown name.  Not thread-safe against
- * concurrent scoring calls.
+ * "list_cap", "cfs_rows_cap", "seg_len", "pass2_generic", "mdr_top_cap",
+ * "mdr_ranks", "mdr_blocks", "mdr_labels").  FS_EINVAL for an unknown name.
+ * Not thread-safe against concurrent scoring calls.
  */
 FS_API int fs_test_hook(const char* name, int64_t value);
 

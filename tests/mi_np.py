@@ -176,6 +176,22 @@ def mixed_columns(n=130, seed=9):
     return X, y, 32
 
 
+def mixed_bound(n, S, seed):
+    """mixed_columns with the state bound at S: a constant column, a column
+    using only codes {0, S - 1}, a 2-state column beside one over 0..S-1 (its
+    first entry S - 1), another constant column, and 6-state noise."""
+    rng = np.random.default_rng(seed)
+    X = rng.integers(0, 6, size=(n, 9)).astype(np.uint8)
+    X[:, 0] = 0
+    X[:, 2] = (S - 1) * rng.integers(0, 2, size=n)
+    X[:, 3] = rng.integers(0, 2, size=n)
+    X[:, 4] = rng.integers(0, S, size=n)
+    X[0, 4] = S - 1
+    X[:, 7] = 3
+    y = rng.integers(0, 4, size=n).astype(np.uint8)
+    return X, y, S
+
+
 # name -> () -> (X, y, n_states): the shapes both backends are checked on
 def _u(n, p, states, seed, y_states=None):
     return lambda: uniform(n, p, states, seed, y_states) + (max(states, y_states or 0),)
@@ -198,3 +214,88 @@ SHAPES = {
     "y4": _u(120, 6, 3, 23, 4),
     "restage": _u(2049, 12, 3, 24),
 }
+
+
+# ---- every lane geometry of the pair-table kernels ---------------------------
+# k_mi_scan, k_mi_row, k_cfs_row, k_jmi_rel, k_jmi_row and k_mi_pack take their
+# thread layout from NB = ceil(states / 4): a pair gets NB^2 lanes, a tile of
+# the scan is T = 16 / NB columns wide and a workgroup of the row kernels holds
+# CPW = 256 / NB^2 columns (250, 252 and 245 of its 256 lanes at NB = 5, 6, 7).
+def nb(states):
+    return (states + 3) // 4
+
+
+def tile(states):
+    return 16 // nb(states)
+
+
+def cpw(states):
+    return 256 // nb(states) ** 2
+
+
+# both ends of every NB in 1..7, the low end of NB = 8, and every count with no
+# padding plane (a multiple of 4)
+GEOMETRY_STATES = (4, 8, 12, 13, 16, 17, 20, 21, 24, 25, 28, 29)
+GEOMETRY_N = (97, 257)
+
+
+def geometry_dims():
+    """(n, p, states): per state count p = CPW - 1 (y, one more column, is the
+    last used lane of the only workgroup), CPW (y alone in a second one),
+    CPW + 1, and 2T + 1 (with y a whole third tile of the scan beside two
+    diagonal and one off-diagonal; the others end in a ragged tile)."""
+    out = []
+    for s in GEOMETRY_STATES:
+        for p in sorted({cpw(s) - 1, cpw(s), cpw(s) + 1, 2 * tile(s) + 1}):
+            out.extend((n, p, s) for n in GEOMETRY_N)
+    return out
+
+
+def geometry_name(n, p, states, classes=None):
+    c = "" if classes is None else "_c%d" % classes
+    return "geo_s%02d%s_p%d_n%d" % (states, c, p, n)
+
+
+def geometry_case(n, p, states, classes=4):
+    """Uniform codes over 0..states-1 and y over 0..classes-1.  With 13 to 29
+    states and 97 or 257 samples many cells and some states stay empty."""
+    return _u(n, p, states, 1000 * states + 10 * p + n % 10 + classes, classes)
+
+
+GEOMETRY = {geometry_name(*d): geometry_case(*d) for d in geometry_dims()}
+GEOMETRY["geo_mixed_s21"] = lambda: mixed_bound(97, 21, 121)
+GEOMETRY["geo_mixed_s25"] = lambda: mixed_bound(257, 25, 125)
+
+# ---- long sample axes --------------------------------------------------------
+# The row kernels stage 64 words (2048 samples) per chunk: one whole chunk, two
+# whole chunks, two chunks and one sample (two restages).
+LONG = {"n%d" % n: _u(n, 5, 3, 30 + n % 7) for n in (2048, 4096, 4097)}
+
+# SHAPES and the two tables above: what both backends are held to
+ALL_SHAPES = {**SHAPES, **GEOMETRY, **LONG}
+
+
+def two_slabs():
+    """(X, y, fold): n = 65535 * 32 + 33, so that word 65536 is the first of a
+    second pack slab (grid.y holds 65535) and the last word is ragged.  Three
+    3-state columns, y the parity of columns 0 and 2 with 20 % flipped, fold
+    ids i % 3."""
+    n = 65535 * 32 + 33
+    rng = np.random.default_rng(77)
+    X = rng.integers(0, 3, size=(n, 3)).astype(np.uint8)
+    y = ((X[:, 0] + X[:, 2]) & 1).astype(np.uint8)
+    y ^= (rng.random(n) < 0.20).astype(np.uint8)
+    fold = (np.arange(n) % 3).astype(np.int32)
+    return X, y, fold
+
+
+_SLABS = []
+
+
+def two_slabs_case():
+    """two_slabs(), built once per session and shared read-only."""
+    if not _SLABS:
+        _SLABS.extend(two_slabs())
+        for a in _SLABS:
+            a.setflags(write=False)
+    return tuple(_SLABS)

@@ -24,7 +24,7 @@ from sklearn.exceptions import NotFittedError
 import cfs_np
 import mi_np
 
-SU_CASES = dict(mi_np.SHAPES)
+SU_CASES = dict(mi_np.ALL_SHAPES)   # with the state counts 4 to 29 and n up to 4097
 SU_CASES["p1"] = lambda: mi_np.uniform(65, 1, 3, 31) + (3,)
 SU_CASES["p2"] = lambda: mi_np.uniform(65, 2, 3, 32) + (3,)
 

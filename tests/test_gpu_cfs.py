@@ -24,6 +24,13 @@ k_cfs_step takes 256 candidates per workgroup.  So:
 * mixed columns: per-column state counts (constant, codes {0, 4}, 2 beside
   32), two constant columns paired (hx + hy < 1e-12 gives 0.0);
 * y with 4 classes beside 3-state columns;
+* 4, 8, 12, 13, 16, 17, 20, 21, 24, 25, 28 and 29 states at n = 97 and 257
+  with a 4-class y (mi_np.GEOMETRY): both ends of every NB = ceil(states / 4),
+  so 16-, 25-, 36- and 49-lane pairs, T = 4, 3, 2 and 10, 7, 5 columns per
+  workgroup with idle lanes, and state counts with no padding plane; per state
+  count p = CPW - 1, CPW, CPW + 1 and 2T + 1; mixed columns with the state
+  bound at 21 and at 25;
+* n = 2048, 4096 and 4097 (mi_np.LONG): whole staging chunks and two restages;
 * fs_cfs_search_matrix at p = 1, 64, 65 (one workgroup, a second one) and
   1000 (four, the last ragged), on random matrices and on matrices in
   multiples of 1/8, where equal merits occur.
@@ -39,7 +46,7 @@ import mi_np
 
 pytestmark = pytest.mark.gpu
 
-SU_CASES = dict(mi_np.SHAPES)
+SU_CASES = dict(mi_np.ALL_SHAPES)
 SU_CASES["p1"] = lambda: mi_np.uniform(65, 1, 3, 31) + (3,)
 SU_CASES["p2"] = lambda: mi_np.uniform(65, 2, 3, 32) + (3,)
 for _p, _s in ((255, 3), (256, 3), (257, 3), (27, 10), (28, 10), (29, 10), (3, 32), (4, 32),
@@ -58,6 +65,8 @@ def L():
 
 def check_su(got, want, what):
     steps = cfs_np.f32_steps(got, want)
+    print(what, "float32 steps", steps.max(initial=0), "differing share",
+          np.count_nonzero(steps) / max(steps.size, 1))
     assert steps.max(initial=0) <= 1, what
     assert np.count_nonzero(steps) <= 0.01 * steps.size, what
 

@@ -21,7 +21,14 @@ not shrink with C.  y is one more column of the planes, it stages 64 words
   and one restaging of LDS;
 * anchors 0, p // 2 and p - 1: both table orientations in every workgroup;
 * mixed columns (a constant column, codes {0, 4} only, 2 beside 32 states) with
-  4 classes of y; a one-class y (no scan); a pair of constant columns.
+  4 classes of y; a one-class y (no scan); a pair of constant columns;
+* 4, 8, 12, 13, 16, 17, 20, 21, 24, 25, 28 and 29 states at n = 97 and 257
+  (mi_np.geometry_dims), each with 2, 3 and 4 classes: both ends of every NB, so
+  16-, 25-, 36- and 49-lane pairs and 10, 7, 5 columns per workgroup with idle
+  lanes; per state count p = CPW - 1, CPW, CPW + 1 and 2T + 1; mixed columns
+  with the state bound at 21 and at 25.  The synthetic-column identity applies
+  at 4 states only; rows and selection are checked on all of them;
+* n = 2048, 4096 and 4097 (mi_np.LONG): whole staging chunks and two restages.
 """
 import numpy as np
 import pytest
@@ -76,6 +83,14 @@ SHAPES.update({
     "one_class": _one_class,
     "constant_pair": _constant_pair,
 })
+GEOMETRY = {}
+for _d in mi_np.geometry_dims():
+    for _c in (2, 3, 4):
+        GEOMETRY[mi_np.geometry_name(*_d, classes=_c)] = mi_np.geometry_case(*_d, classes=_c)
+GEOMETRY["geo_mixed_s21"] = mi_np.GEOMETRY["geo_mixed_s21"]
+GEOMETRY["geo_mixed_s25"] = mi_np.GEOMETRY["geo_mixed_s25"]
+SHAPES.update(GEOMETRY)
+SHAPES.update(mi_np.LONG)
 
 _DATA = {}
 
@@ -118,7 +133,7 @@ def test_rows(L, name):
 
 
 SELECT = ["s3_c2_p257", "s3_c3_p256", "s3_c4_p255", "s5_c2_p130", "s10_c2_p29", "s32_c4_p9",
-          "mixed_c4", "n2049", "one_class", "constant_pair"]
+          "mixed_c4", "n2049", "one_class", "constant_pair"] + sorted(GEOMETRY)
 
 
 @pytest.mark.parametrize("name", SELECT)

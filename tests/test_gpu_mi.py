@@ -13,7 +13,14 @@ and it stages 64 words (2048 samples) per chunk, so:
 * 2, 5, 10 and 32 states: 1, 4, 9 and 64 lanes per pair, T = 16, 8, 5, 2;
 * mixed columns: per-column state counts (constant, codes {0, 4}, 2 beside 32);
 * y with 4 classes beside 3-state columns;
-* n = 2049: the word loop restages LDS once."""
+* n = 2049: the word loop restages LDS once;
+* 4, 8, 12, 13, 16, 17, 20, 21, 24, 25, 28 and 29 states at n = 97 and 257
+  with a 4-class y (mi_np.GEOMETRY): both ends of every NB = ceil(states / 4),
+  so 16-, 25-, 36- and 49-lane pairs, T = 4, 3, 2 and 10, 7, 5 columns per
+  workgroup with idle lanes, and state counts with no padding plane; per state
+  count p = CPW - 1, CPW, CPW + 1 and 2T + 1; mixed columns with the state
+  bound at 21 and at 25;
+* n = 2048, 4096 and 4097 (mi_np.LONG): whole staging chunks and two restages."""
 import ctypes
 
 import numpy as np
@@ -34,11 +41,13 @@ def L():
     return _lib
 
 
-@pytest.mark.parametrize("name", sorted(mi_np.SHAPES))
+@pytest.mark.parametrize("name", sorted(mi_np.ALL_SHAPES))
 def test_matrices_equal_cpu_and_numpy(L, name):
-    X, y, S, rel, red, cnt = mi_np.case(name, mi_np.SHAPES[name])
+    X, y, S, rel, red, cnt = mi_np.case(name, mi_np.ALL_SHAPES[name])
     gr, gR, gc = L.mi_matrices("gpu", X, y, S, want_counts=True)
     cr, cR, cc = L.mi_matrices("cpu", X, y, S, want_counts=True)
+    print(name, "gpu-numpy", max(np.abs(gr - rel).max(), np.abs(gR - red).max()),
+          "gpu-cpu", max(np.abs(gr - cr).max(), np.abs(gR - cR).max()))
     assert np.array_equal(gc, cnt)
     assert np.array_equal(gc, cc)
     assert np.abs(gr - rel).max() <= TOL and np.abs(gR - red).max() <= TOL
@@ -66,11 +75,14 @@ def test_relevance_only(L):
     assert np.abs(r - rel).max() <= TOL
 
 
-@pytest.mark.parametrize("name,tiles", [("states32", 7), ("p130", 10), ("p34_tile16", 1)])
+@pytest.mark.parametrize("name,tiles", [("states32", 7), ("p130", 10), ("p34_tile16", 1),
+                                        ("geo_s16_p17_n257", 4), ("geo_s20_p11_n97", 3),
+                                        ("geo_s24_p8_n257", 4), ("geo_s28_p6_n97", 3)])
 def test_several_launches(L, name, tiles):
     """The tile range split over launches (the mi_tiles hook: 66 tiles by 7,
-    45 by 10, 6 one by one) gives the bits and tables of one launch."""
-    X, y, S, _, _, cnt = mi_np.case(name, mi_np.SHAPES[name])
+    45 by 10, 6 one by one; at NB = 4, 5, 6, 7 15 tiles by 4, 10 by 3, 15 by 4,
+    10 by 3) gives the bits and tables of one launch."""
+    X, y, S, _, _, cnt = mi_np.case(name, mi_np.ALL_SHAPES[name])
     r1, R1 = L.mi_matrices("gpu", X, y, S)
     with L.test_hooks(mi_tiles=tiles):
         r2, R2, c2 = L.mi_matrices("gpu", X, y, S, want_counts=True)

@@ -14,7 +14,14 @@ use 256 lanes:
 * 10 states: p = 29 (28 pairs per workgroup, 4 idle lanes); 32 states: p = 9;
 * mixed columns: per-column state counts; y with 4 classes beside 3 states;
 * n = 33 / 64 / 203 / 2049: over a word boundary, whole words, a ragged word,
-  and one restaging of LDS."""
+  and one restaging of LDS;
+* 4, 8, 12, 13, 16, 17, 20, 21, 24, 25, 28 and 29 states at n = 97 and 257
+  with a 4-class y (mi_np.GEOMETRY): both ends of every NB = ceil(states / 4),
+  so 16-, 25-, 36- and 49-lane pairs, T = 4, 3, 2 and 10, 7, 5 columns per
+  workgroup with idle lanes, and state counts with no padding plane; per state
+  count p = CPW - 1, CPW, CPW + 1 and 2T + 1; mixed columns with the state
+  bound at 21 and at 25;
+* n = 2048, 4096 and 4097 (mi_np.LONG): whole staging chunks and two restages."""
 import numpy as np
 import pytest
 
@@ -54,6 +61,8 @@ SHAPES = {
     "n203": mi_np.SHAPES["n203"],
     "n2049": mi_np.SHAPES["restage"],
 }
+SHAPES.update(mi_np.GEOMETRY)
+SHAPES.update(mi_np.LONG)
 
 _MATS = {}
 
@@ -82,6 +91,7 @@ def _check_data_path(L, X, y, S, rel, red, k):
         assert none is None and np.array_equal(sel3, sel) and np.array_equal(r3, r)
     # the CPU backend's values of the same rows (the last method's selection)
     cr, cR = L.mi_matrices("cpu", X, y, S)
+    print("gpu-cpu", max(np.abs(r - cr).max(), np.abs(rows - cR[sel]).max()))
     assert np.abs(r - cr).max() <= TOL and np.abs(rows - cR[sel]).max() <= TOL
 
 

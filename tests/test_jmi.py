@@ -22,6 +22,9 @@ the shapes used here (at most 257 non-zero terms) more than 100x, while a
 wrong count moves a value by about 1/n >= 5e-4.  The restatement's stated
 deviation (about -1e-12 per non-zero cell of a table with a single row or a
 single class) stays inside it for the shapes used: at most 25 such cells.
+
+The shapes are mi_np.ALL_SHAPES, the state counts 4 to 29 of mi_np.GEOMETRY
+(4 classes of y) and the long sample axes of mi_np.LONG included.
 """
 import numpy as np
 import pytest
@@ -41,7 +44,7 @@ def _case(name):
     """(X, y, S, C, anchors, rows of the CPU backend at every column), once per
     session."""
     if name not in _CASES:
-        X, y, S = mi_np.SHAPES[name]()
+        X, y, S = mi_np.ALL_SHAPES[name]()
         X = np.ascontiguousarray(X, dtype=np.uint8)
         y = np.ascontiguousarray(y, dtype=np.uint8)
         p = X.shape[1]
@@ -51,7 +54,7 @@ def _case(name):
     return _CASES[name]
 
 
-@pytest.mark.parametrize("name", sorted(mi_np.SHAPES))
+@pytest.mark.parametrize("name", sorted(mi_np.ALL_SHAPES))
 def test_rows_equal_restatement(name):
     X, y, S, C, anchors, allrows = _case(name)
     want = jmi_np.rows(X, y, anchors, S, C)
@@ -64,8 +67,9 @@ def test_rows_equal_restatement(name):
     assert np.array_equal(L.jmi_rows("cpu", X, y, S, anchors, n_jobs=1), got)
 
 
-@pytest.mark.parametrize("name", sorted(n for n in mi_np.SHAPES
-                                        if n not in ("states32", "mixed")))
+# the synthetic columns need S^2 <= 256 states: every shape up to 16 states
+@pytest.mark.parametrize("name", sorted(n for n, make in mi_np.ALL_SHAPES.items()
+                                        if make()[2] ** 2 <= 256))
 def test_rows_equal_relevance_of_synthetic_columns(name):
     X, y, S, C, anchors, allrows = _case(name)
     assert S * S <= 256
@@ -87,7 +91,7 @@ def test_nat_unit():
 
 
 @pytest.mark.parametrize("method", jmi_np.METHODS)
-@pytest.mark.parametrize("name", sorted(mi_np.SHAPES))
+@pytest.mark.parametrize("name", sorted(mi_np.ALL_SHAPES))
 def test_select_equals_greedy_on_own_rows(name, method):
     X, y, S, C, anchors, allrows = _case(name)
     p = X.shape[1]

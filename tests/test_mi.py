@@ -8,6 +8,10 @@ sum(pxy) = 1: a few ulps per term plus a <= 1 ulp log bound the error of the
 sum near 4e-12 bits for n < 2^31, so the absolute 1e-10 used here leaves
 about 25x over that bound, and a wrong count (which moves MI by about 1/n or
 more) cannot hide in it.
+
+The shapes are mi_np.ALL_SHAPES: the GPU tests' own (test_gpu_mi.py lists
+them), the state counts 4 to 29 of mi_np.GEOMETRY and the long sample axes of
+mi_np.LONG included.
 """
 import math
 
@@ -20,10 +24,10 @@ import mi_np
 TOL = 1e-10
 
 
-@pytest.mark.parametrize("name", sorted(mi_np.SHAPES))
+@pytest.mark.parametrize("name", sorted(mi_np.ALL_SHAPES))
 def test_cpu_backend_equals_numpy(name):
     from fastselect_amd import _lib
-    X, y, S, rel, red, cnt = mi_np.case(name, mi_np.SHAPES[name])
+    X, y, S, rel, red, cnt = mi_np.case(name, mi_np.ALL_SHAPES[name])
     r, R, c = _lib.mi_matrices("cpu", X, y, S, want_counts=True)
     assert np.array_equal(c, cnt)
     assert np.abs(r - rel).max() <= TOL

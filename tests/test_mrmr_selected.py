@@ -33,7 +33,8 @@ def _planted(n, p, states, seed):
     return make
 
 
-DATA = {name: mi_np.SHAPES[name] for name in sorted(mi_np.SHAPES)}
+# with the state counts 4 to 29 (mi_np.GEOMETRY) and n up to 4097 (mi_np.LONG)
+DATA = {name: mi_np.ALL_SHAPES[name] for name in sorted(mi_np.ALL_SHAPES)}
 DATA.update({"planted_%d_%d_%d_%d" % c: _planted(*c) for c in mi_np.PLANTED})
 
 
