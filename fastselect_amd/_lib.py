@@ -56,6 +56,7 @@ EXPORTED = (
     "fs_cfs_last_timing", "fs_cfs_destroy",
     "fs_mrmr_select", "fs_mrmr_search_matrix", "fs_mrmr_last_timing",
     "fs_jmi_select", "fs_jmi_rows", "fs_jmi_search_matrix", "fs_jmi_last_timing",
+    "fs_pair_screen", "fs_pair_screen_last_timing",
 )
 
 
@@ -213,6 +214,11 @@ def _load() -> ctypes.CDLL:
     lib.fs_jmi_last_timing.argtypes = [_f64p]
     for name in ("fs_jmi_select", "fs_jmi_rows", "fs_jmi_search_matrix", "fs_jmi_last_timing"):
         getattr(lib, name).restype = _int
+    lib.fs_pair_screen.argtypes = [_int, _int, _u8p, _u8p, _i64, _i64, _int, _int, _int, _i64, _int,
+                                   _f64p, _f64p, _i64p, _i64p, _f64p]
+    lib.fs_pair_screen.restype = _int
+    lib.fs_pair_screen_last_timing.argtypes = [_f64p]
+    lib.fs_pair_screen_last_timing.restype = _int
     for name in ("fs_column_stats", "fs_multisurf_score", "fs_multisurf_score_rows",
                  "fs_plan_set_rows", "fs_relieff_score", "fs_surf_score",
                  "fs_relieff_score_rows", "fs_surf_score_rows", "fs_plan_create",
@@ -1170,4 +1176,48 @@ def jmi_last_timing():
     last GPU ``jmi_select`` (``fs_jmi_last_timing``; -1 where unavailable)."""
     v = np.full(5, -1.0)
     check(_lib.fs_jmi_last_timing(_p(v, _f64p)))
+    return tuple(float(t) for t in v)
+
+
+PAIR_SCORES = {"joint": 0, "gain": 1}
+PAIR_MAX_TOP = 65536
+
+
+def pair_screen(backend, codes, ycodes, n_states, n_top=100, score="gain", unit="bit", n_jobs=-1,
+                device=0, want_feature_best=True):
+    """The ``n_top`` best of all C(p,2) column pairs (``fs_pair_screen``) by
+    joint relevance ``J(i, j) = I(X_i, X_j; y)`` (``score="joint"``) or by the
+    interaction gain ``(J(i, j) - rel[i]) - rel[j]`` (``score="gain"``), ordered
+    by (score descending, rank in ``itertools.combinations`` ascending).
+
+    ``codes`` (n x p) and ``ycodes`` (n) hold values in ``0..n_states-1``
+    (uint8).  Returns (relevance float64 [p], top_score float64 [m], top_pairs
+    int64 [m, 2] with i < j, feature_best float64 [p]: the largest score of any
+    pair that contains the feature, or None without ``want_feature_best``), with
+    ``m = min(n_top, C(p,2))``."""
+    x, yv = _jmi_codes(codes, ycodes, unit)
+    n, p = x.shape
+    if score not in PAIR_SCORES:
+        raise ValueError("score must be 'joint' or 'gain'")
+    n_top = int(n_top)
+    size = min(max(n_top, 1), PAIR_MAX_TOP)
+    rel = np.zeros(p, dtype=np.float64)
+    top_s = np.zeros(size, dtype=np.float64)
+    top_i = np.full(size, -1, dtype=np.int64)
+    top_j = np.full(size, -1, dtype=np.int64)
+    fb = np.zeros(p, dtype=np.float64) if want_feature_best else None
+    check(_lib.fs_pair_screen(_backend_code(backend), int(device), _p(x, _u8p), _p(yv, _u8p), n, p,
+                              int(n_states), MI_UNITS[unit], PAIR_SCORES[score], n_top,
+                              int(n_jobs), _p(rel, _f64p), _p(top_s, _f64p), _p(top_i, _i64p),
+                              _p(top_j, _i64p), None if fb is None else _p(fb, _f64p)))
+    m = min(n_top, p * (p - 1) // 2)
+    return rel, top_s[:m], np.stack([top_i[:m], top_j[:m]], axis=1), fb
+
+
+def pair_screen_last_timing():
+    """(upload, pack, relevance, scan with selection, download) milliseconds of
+    this thread's last GPU ``pair_screen`` (``fs_pair_screen_last_timing``; -1
+    where unavailable)."""
+    v = np.full(5, -1.0)
+    check(_lib.fs_pair_screen_last_timing(_p(v, _f64p)))
     return tuple(float(t) for t in v)

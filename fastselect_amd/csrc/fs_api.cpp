@@ -13,6 +13,7 @@
 #include "fs_mdr.h"
 #include "fs_mi.h"
 #include "fs_mrmr.h"
+#include "fs_pairscan.h"
 
 #include <chrono>
 #include <cstdio>
@@ -165,6 +166,8 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "mdr_ranks") h.mdr_ranks = value;
   else if (k == "mdr_blocks") h.mdr_blocks = value;
   else if (k == "mdr_labels") h.mdr_labels = value;
+  else if (k == "pair_tiles") h.pair_tiles = value;
+  else if (k == "pair_cap") h.pair_cap = value;
   else {
     set_error("fs_test_hook: unknown hook '" + k + "'");
     return FS_EINVAL;
@@ -505,6 +508,38 @@ int fs_surf_score_devices(const int* devices, int n_devices, const double* x, in
   if (rc != FS_OK) return rc;
   return surf_sums(FS_BACKEND_GPU, devices[0], x, n, p, y, recip, use_star, is_discrete, n_jobs,
                    row_begin, row_end, sums_out, devices, n_devices);
+}
+
+int fs_pair_screen(int backend, int device, const uint8_t* codes, const uint8_t* ycodes, int64_t n,
+                   int64_t p, int n_states, int unit, int score_kind, int64_t n_top, int n_jobs,
+                   double* relevance, double* top_score, int64_t* top_i, int64_t* top_j,
+                   double* feature_best) {
+  if (backend != FS_BACKEND_CPU && backend != FS_BACKEND_GPU) {
+    set_error("backend must be FS_BACKEND_CPU or FS_BACKEND_GPU");
+    return FS_EINVAL;
+  }
+  // the argument checks come before the device check, as in fs_jmi_select
+  int rc = pair_check(backend, codes, ycodes, n, p, n_states, unit, score_kind, n_top, relevance,
+                      top_score, top_i, top_j);
+  if (rc != FS_OK) return rc;
+  // so do the GPU backend's size and class limits
+  if (backend == FS_BACKEND_GPU && (rc = gpu::pair_limits(ycodes, n, p, n_states)) != FS_OK)
+    return rc;
+  if ((rc = check_backend(backend, device)) != FS_OK) return rc;
+  if (backend == FS_BACKEND_GPU)
+    return gpu::pair_screen(device, codes, ycodes, n, p, n_states, unit, score_kind, (int)n_top,
+                            relevance, top_score, top_i, top_j, feature_best);
+  return cpu::pair_screen(codes, ycodes, n, p, n_states, unit, score_kind, (int)n_top, n_jobs,
+                          relevance, top_score, top_i, top_j, feature_best);
+}
+
+int fs_pair_screen_last_timing(double* ms5) {
+  if (!ms5) {
+    set_error("fs_pair_screen_last_timing: NULL output");
+    return FS_EINVAL;
+  }
+  gpu::pair_last_timing(ms5);
+  return FS_OK;
 }
 
 }  // extern "C"

@@ -152,6 +152,8 @@ struct TestHooks {
   int64_t mdr_ranks = 0;       // >= 1: ranks per launch of the three MDR scans, no 65536 floor (fs_mdr.hip)
   int64_t mdr_blocks = 0;      // >= 1: blocks (rank runs) per launch of the three MDR scans at most
   int64_t mdr_labels = 0;      // >= 64: labellings per launch of fs_mdr_scan_labels, taken down to a multiple of 64
+  int64_t pair_tiles = 0;      // >= 1: tiles per launch of the pair screen's scan (fs_pairscan.hip)
+  int64_t pair_cap = 0;        // >= 1: candidates the pair screen's device buffer holds, 256 (one tile's pairs) at least
 };
 TestHooks& test_hooks();
 

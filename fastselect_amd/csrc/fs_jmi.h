@@ -90,6 +90,14 @@ int jmi_check_matrix(const double* relevance, const double* joint, int64_t p, in
                      int64_t k, const int64_t* selected);
 
 namespace cpu {
+// The pieces of a row that fs_pairscan_cpu.cpp takes as they are
+// (fs_jmi_cpu.cpp): the joint table of the pair i < j with y,
+// tab[(a * kcol[j] + b) * kcol[y] + c]; the cells of the largest joint table
+// (FS_EINVAL beyond kJmiMaxCellsCpu; `who` opens the message); and
+// out[c] = I(X_c; y) for c < p.
+void joint_table(const MiColumns& m, int64_t i, int64_t j, int32_t* tab);
+int joint_cells(const MiColumns& m, const char* who, int64_t& cells);
+void rel_row(const MiColumns& m, int unit, int n_jobs, double* out);
 int jmi_select(const uint8_t* codes, const uint8_t* ycodes, int64_t n, int64_t p, int n_states,
                int unit, int method, int64_t k, int n_jobs, double* relevance, int64_t* selected,
                double* rows);

@@ -147,6 +147,9 @@ FS_JMI_POPCNT void joint_planes_hw(const uint64_t* pi, const uint64_t* pj, const
   joint_planes<true>(pi, pj, py, W, ki, kj, ky, tab);
 }
 
+}  // namespace
+
+// joint_table, joint_cells and rel_row are fs_pairscan_cpu.cpp's too (fs_jmi.h).
 // The joint table of the pair i < j with y: tab[(a * kcol[j] + b) * kcol[y] + c].
 void joint_table(const MiColumns& m, int64_t i, int64_t j, int32_t* tab) {
   static const auto tabfn = have_popcnt() ? joint_planes_hw : joint_planes_sw;
@@ -200,6 +203,8 @@ void rel_row(const MiColumns& m, int unit, int n_jobs, double* out) {
   work();
   for (auto& t : th) t.join();
 }
+
+namespace {
 
 // out[c] = J(c, anchor) for c < p, 0.0 at c == anchor.  The column with the
 // lower index supplies the joint state's high digit.

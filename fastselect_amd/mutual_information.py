@@ -135,3 +135,36 @@ def calculate_joint_relevance(X, y, anchors, *, backend="auto", unit="bit", n_jo
     where = _choose_backend_joint(backend, max_state, int(y_d.max()) + 1)
     return _lib.jmi_rows(where, X_d, y_d, max_state, anchors, unit=unit, n_jobs=n_jobs,
                          device=device)
+
+
+def rank_pair_interactions(X, y, n_top=100, *, score="gain", backend="auto", unit="bit", n_jobs=-1,
+                           device=0):
+    """The ``n_top`` best of all C(p,2) column pairs of integer-coded X (n x p)
+    by what they say about y (n) together (``fs_pair_screen``): an exhaustive
+    scan, returned as a ranked list and never as a p x p matrix.
+
+    ``score="joint"`` ranks by the joint relevance ``J(i, j) = I(X_i, X_j; y)``,
+    the quantity of ``calculate_joint_relevance``; ``score="gain"`` by the
+    interaction information ``(J(i, j) - I(X_i; y)) - I(X_j; y)``, positive for
+    a pair that says more together than apart.  The list is ordered by (score
+    descending, place in ``itertools.combinations(range(p), 2)`` ascending).
+
+    Returns (top_pairs int64 [m, 2] with i < j, top_scores float64 [m],
+    relevance float64 [p], feature_best float64 [p]: the largest score of any
+    pair that contains the feature), ``m = min(n_top, C(p,2))``.  Not a
+    reference function."""
+    X = np.asarray(X)
+    y = np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1 or X.shape[0] != y.shape[0]:
+        raise ValueError("X must be 2‑D and y 1‑D with matching sample size")
+    X_d = _validate_discrete(X, "X")
+    y_d = _validate_discrete(y, "y")
+    if X.shape[1] < 2:
+        raise ValueError("X must have at least two columns")
+    if not (1 <= int(n_top) <= _lib.PAIR_MAX_TOP):
+        raise ValueError(f"n_top must be in 1..{_lib.PAIR_MAX_TOP}")
+    max_state = int(max(X_d.max(), y_d.max())) + 1
+    where = _choose_backend_joint(backend, max_state, int(y_d.max()) + 1)
+    rel, top_s, top_p, best = _lib.pair_screen(where, X_d, y_d, max_state, n_top=n_top, score=score,
+                                               unit=unit, n_jobs=n_jobs, device=device)
+    return top_p, top_s, rel, best

@@ -118,7 +118,7 @@ FS_API int fs_get_accumulation(void);
  * "rf_xlds", "rf_fcap", "ties_1w", "ties_coop", "rf_ref_replay", "ref_q16", "surf_f64",
  * "colsort_bins12", "colsort_global", "star_split", "colsort_star", "mi_tiles",
  * "list_cap", "cfs_rows_cap", "seg_len", "pass2_generic", "mdr_top_cap",
- * "mdr_ranks", "mdr_blocks", "mdr_labels").  FS_EINVAL for an unknown name.
+ * "mdr_ranks", "mdr_blocks", "mdr_labels", "pair_tiles", "pair_cap").  FS_EINVAL for an unknown name.
  * Not thread-safe against concurrent scoring calls.
  */
 FS_API int fs_test_hook(const char* name, int64_t value);
@@ -792,6 +792,49 @@ FS_API int fs_jmi_search_matrix(int backend, int device, const double* relevance
  * unavailable: above 64 steps the loop is timed as a whole, in `rows`), for
  * the benchmark tool. */
 FS_API int fs_jmi_last_timing(double* ms5);
+
+/* ---- Pair screen: the n_top best of all pairs by joint relevance ---------- */
+
+/*
+ * An exhaustive scan of the joint relevance J(i, j) = I(X_i, X_j; y) of
+ * fs_jmi_select over all C(p,2) pairs i < j, returned as a ranked list, not a
+ * matrix: it finds a pair that acts purely together (y = x_a XOR x_b), which
+ * no marginal or greedy selector reaches.  J(i, j) has, on the same backend,
+ * the bits fs_jmi_rows gives for (c = j, anchor = i).  The score of a pair is
+ *   score_kind 0 ("joint"):  J(i, j);
+ *   score_kind 1 ("gain"):   (J(i, j) - relevance[i]) - relevance[j] in float64
+ *                            in that order (the interaction information:
+ *                            positive for synergy, negative for redundancy).
+ * The list is ordered by (score descending, rank ascending), the rank of a
+ * pair being its place in itertools.combinations(range(p), 2),
+ * i * (2p - i - 1) / 2 + (j - i - 1); there is no closeness rule, and -0.0
+ * counts (and is returned) as +0.0.
+ *   relevance     [p]: I(X_f; y), the bits of fs_mi_matrices / fs_jmi_select
+ *   top_score     [n_top], top_i, top_j [n_top]: the first min(n_top, C(p,2))
+ *                 pairs in that order; the entries past C(p,2) are score 0.0,
+ *                 i = j = -1 (as fs_mdr_scan_top)
+ *   feature_best  NULL, or [p]: the largest score of any pair that contains f
+ *   n_top         1..65536
+ *   n_jobs        CPU threads (-1 = all); ignored by the GPU backend
+ * The result is identical for every thread count, launch split and buffer
+ * size.  codes, ycodes, n, p, n_states, unit: as fs_jmi_select.  FS_EINVAL:
+ * as fs_jmi_select, and p < 2, n_top outside 1..65536, score_kind outside
+ * 0..1, NULL relevance / top_score / top_i / top_j; on the CPU backend a joint
+ * table of more than 2^20 cells; on the GPU backend more than 32 states or
+ * more than 4 classes of y (a one-class y gives all-zero scores without a
+ * scan).  Device memory is the bit-planes plus O(p + n_top): nothing of size
+ * p x p.  FS_EOOM when the planes do not fit (decided before any array is
+ * read).
+ */
+FS_API int fs_pair_screen(int backend, int device, const uint8_t* codes, const uint8_t* ycodes,
+                          int64_t n, int64_t p, int n_states, int unit, int score_kind,
+                          int64_t n_top, int n_jobs, double* relevance, double* top_score,
+                          int64_t* top_i, int64_t* top_j, double* feature_best);
+/* Milliseconds the calling thread's last GPU fs_pair_screen spent on upload,
+ * pack, relevance, the scan with the selection (its launches and the host
+ * merges between them) and download (HIP events; -1 where unavailable), for
+ * the benchmark tool. */
+FS_API int fs_pair_screen_last_timing(double* ms5);
 
 #ifdef __cplusplus
 }
