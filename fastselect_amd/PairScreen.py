@@ -68,6 +68,8 @@ class PairScreen(TransformerMixin, BaseEstimator):
     top_features_ : ndarray of int32, shape (n_features_to_select,)
         The first of ``np.argsort(-interaction_scores_, kind="stable")``.
     n_features_in_, effective_backend_
+    null_max_scores_, null_best_pairs_, n_permutations_, p_value_, top_p_values_
+        After ``permutation_test`` only: see there.
     """
 
     def __init__(self, n_features_to_select: int, n_top: int = 100, score: str = "gain",
@@ -82,6 +84,11 @@ class PairScreen(TransformerMixin, BaseEstimator):
 
     def fit(self, X, y):
         """Screen all pairs of the discrete X and keep the best features."""
+        self._fit_codes(X, y)
+        return self
+
+    def _fit_codes(self, X, y):
+        """``fit``; returns what it made of X and y: (codes, ycodes, n_states)."""
         if self.score not in _lib.PAIR_SCORES:
             raise ValueError("score must be either 'gain' or 'joint'.")
         if self.backend not in ("auto", "cpu", "gpu"):
@@ -131,6 +138,50 @@ class PairScreen(TransformerMixin, BaseEstimator):
         self.feature_importances_ = self.interaction_scores_
         order = np.argsort(-self.interaction_scores_, kind="stable")
         self.top_features_ = order[:self.n_features_to_select].astype(np.int32)
+        return codes, ycodes, n_states
+
+    def permutation_test(self, X, y, n_permutations=1000, random_state=None):
+        """``fit``, then the max-T (Westfall-Young single-step) permutation test
+        of the ranked list: an exhaustive screen finds a best pair in pure
+        noise too, and this says how large the best score of a screen gets
+        when y has nothing to do with X.
+
+        The screen of y and of ``n_permutations`` shuffles of y
+        (``np.random.default_rng(random_state).permutation``, in order) is one
+        pass over the pairs (``fs_pair_screen_labels``); the null statistic of
+        a shuffle is the best score of its whole screen.  Every attribute of
+        ``fit`` is set as ``fit`` sets it, and
+
+        * ``null_max_scores_`` (n_permutations,), ``null_best_pairs_``
+          (n_permutations, 2), ``n_permutations_``;
+        * ``p_value_``: ``(1 + #{null_max >= top_scores_[0]}) / (1 + n_permutations)``;
+        * ``top_p_values_``: the same for every listed pair, the max-T adjusted
+          p-value of each; non-decreasing down the list.
+        """
+        if not (isinstance(n_permutations, (int, np.integer)) and
+                1 <= n_permutations < _lib.PAIR_MAX_LABELINGS):
+            raise ValueError(f"n_permutations must be in 1..{_lib.PAIR_MAX_LABELINGS - 1}")
+        n_perm = int(n_permutations)
+        codes, ycodes, n_states = self._fit_codes(X, y)
+        rng = np.random.default_rng(random_state)
+        labels = np.empty((n_perm + 1, ycodes.size), dtype=np.uint8)
+        labels[0] = ycodes
+        for b in range(1, n_perm + 1):
+            labels[b] = rng.permutation(ycodes)
+        best, pairs, _ = _lib.pair_screen_labels(
+            self.effective_backend_, codes, labels, n_states, score=self.score, unit=self.unit,
+            n_jobs=self.n_jobs, device=self.device)
+        # row 0 is the data's own y: the batch and the single call agree bit for bit
+        if best[0] != self.top_scores_[0] or tuple(pairs[0]) != tuple(self.top_pairs_[0]):
+            raise AssertionError(
+                "fs_pair_screen_labels disagrees with fs_pair_screen on the unpermuted y")
+        self.null_max_scores_ = best[1:].copy()
+        self.null_best_pairs_ = pairs[1:].copy()
+        self.n_permutations_ = n_perm
+        null_sorted = np.sort(self.null_max_scores_)
+        at_least = n_perm - np.searchsorted(null_sorted, self.top_scores_, side="left")
+        self.top_p_values_ = (1.0 + at_least) / (1.0 + n_perm)
+        self.p_value_ = float(self.top_p_values_[0])
         return self
 
     def transform(self, X):

@@ -57,6 +57,7 @@ EXPORTED = (
     "fs_mrmr_select", "fs_mrmr_search_matrix", "fs_mrmr_last_timing",
     "fs_jmi_select", "fs_jmi_rows", "fs_jmi_search_matrix", "fs_jmi_last_timing",
     "fs_pair_screen", "fs_pair_screen_last_timing",
+    "fs_pair_screen_labels", "fs_pair_labels_last_timing",
 )
 
 
@@ -219,6 +220,11 @@ def _load() -> ctypes.CDLL:
     lib.fs_pair_screen.restype = _int
     lib.fs_pair_screen_last_timing.argtypes = [_f64p]
     lib.fs_pair_screen_last_timing.restype = _int
+    lib.fs_pair_screen_labels.argtypes = [_int, _int, _u8p, _u8p, _int, _i64, _i64, _int, _int,
+                                          _int, _int, _f64p, _i64p, _i64p, _f64p]
+    lib.fs_pair_screen_labels.restype = _int
+    lib.fs_pair_labels_last_timing.argtypes = [_f64p]
+    lib.fs_pair_labels_last_timing.restype = _int
     for name in ("fs_column_stats", "fs_multisurf_score", "fs_multisurf_score_rows",
                  "fs_plan_set_rows", "fs_relieff_score", "fs_surf_score",
                  "fs_relieff_score_rows", "fs_surf_score_rows", "fs_plan_create",
@@ -1220,4 +1226,53 @@ def pair_screen_last_timing():
     where unavailable)."""
     v = np.full(5, -1.0)
     check(_lib.fs_pair_screen_last_timing(_p(v, _f64p)))
+    return tuple(float(t) for t in v)
+
+
+PAIR_MAX_LABELINGS = 65535
+
+
+def pair_screen_labels(backend, codes, labels, n_states, score="gain", unit="bit", n_jobs=-1,
+                       device=0, want_relevance=False):
+    """The best pair of the pair screen under each of B labellings of y in one
+    pass (``fs_pair_screen_labels``): row b is what
+    ``pair_screen(backend, codes, labels[b], n_states, n_top=1)`` returns first,
+    bit for bit on the same backend.
+
+    ``codes`` (n x p) and ``labels`` (B x n) hold values in ``0..n_states-1``
+    (uint8); the rows of ``labels`` are arbitrary.  Returns (best_score float64
+    [B], best_pairs int64 [B, 2] with i < j, relevance float64 [B, p] or None
+    without ``want_relevance``)."""
+    x = np.ascontiguousarray(codes, dtype=np.uint8)
+    if x.ndim != 2:
+        raise ValueError("codes must be a 2-D array")
+    lab = np.ascontiguousarray(labels, dtype=np.uint8)
+    if lab.ndim != 2 or lab.shape[1] != x.shape[0]:
+        raise ValueError("labels must be a 2-D array with one column per row of codes")
+    if unit not in MI_UNITS:
+        raise ValueError("unit must be 'bit' or 'nat'")
+    if score not in PAIR_SCORES:
+        raise ValueError("score must be 'joint' or 'gain'")
+    n, p = x.shape
+    B = lab.shape[0]
+    if not (1 <= B <= PAIR_MAX_LABELINGS):
+        raise ValueError(f"the number of labellings must be in 1..{PAIR_MAX_LABELINGS}")
+    best_s = np.zeros(B, dtype=np.float64)
+    best_i = np.full(B, -1, dtype=np.int64)
+    best_j = np.full(B, -1, dtype=np.int64)
+    rel = np.zeros((B, p), dtype=np.float64) if want_relevance else None
+    check(_lib.fs_pair_screen_labels(_backend_code(backend), int(device), _p(x, _u8p),
+                                     _p(lab, _u8p), B, n, p, int(n_states), MI_UNITS[unit],
+                                     PAIR_SCORES[score], int(n_jobs), _p(best_s, _f64p),
+                                     _p(best_i, _i64p), _p(best_j, _i64p),
+                                     None if rel is None else _p(rel, _f64p)))
+    return best_s, np.stack([best_i, best_j], axis=1), rel
+
+
+def pair_labels_last_timing():
+    """(upload, pack, relevance, scan with reduction, download) milliseconds of
+    this thread's last GPU ``pair_screen_labels``
+    (``fs_pair_labels_last_timing``; -1 where unavailable)."""
+    v = np.full(5, -1.0)
+    check(_lib.fs_pair_labels_last_timing(_p(v, _f64p)))
     return tuple(float(t) for t in v)

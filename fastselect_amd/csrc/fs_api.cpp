@@ -168,6 +168,8 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "mdr_labels") h.mdr_labels = value;
   else if (k == "pair_tiles") h.pair_tiles = value;
   else if (k == "pair_cap") h.pair_cap = value;
+  else if (k == "pair_labels") h.pair_labels = value;
+  else if (k == "pair_lab_ranks") h.pair_lab_ranks = value;
   else {
     set_error("fs_test_hook: unknown hook '" + k + "'");
     return FS_EINVAL;
@@ -539,6 +541,40 @@ int fs_pair_screen_last_timing(double* ms5) {
     return FS_EINVAL;
   }
   gpu::pair_last_timing(ms5);
+  return FS_OK;
+}
+
+int fs_pair_screen_labels(int backend, int device, const uint8_t* codes, const uint8_t* labels,
+                          int n_labelings, int64_t n, int64_t p, int n_states, int unit,
+                          int score_kind, int n_jobs, double* best_score, int64_t* best_i,
+                          int64_t* best_j, double* relevance) {
+  if (backend != FS_BACKEND_CPU && backend != FS_BACKEND_GPU) {
+    set_error("backend must be FS_BACKEND_CPU or FS_BACKEND_GPU");
+    return FS_EINVAL;
+  }
+  // the argument checks come before the device check, as in fs_pair_screen
+  int rc = pair_labels_check(backend, codes, labels, n_labelings, n, p, n_states, unit,
+                             score_kind, best_score, best_i, best_j);
+  if (rc != FS_OK) return rc;
+  // so do the GPU backend's size and class limits
+  int classes = 0;
+  if (backend == FS_BACKEND_GPU &&
+      (rc = gpu::pair_labels_limits(labels, n_labelings, n, p, n_states, &classes)) != FS_OK)
+    return rc;
+  if ((rc = check_backend(backend, device)) != FS_OK) return rc;
+  if (backend == FS_BACKEND_GPU)
+    return gpu::pair_screen_labels(device, codes, labels, n_labelings, classes, n, p, n_states,
+                                   unit, score_kind, best_score, best_i, best_j, relevance);
+  return cpu::pair_screen_labels(codes, labels, n_labelings, n, p, n_states, unit, score_kind,
+                                 n_jobs, best_score, best_i, best_j, relevance);
+}
+
+int fs_pair_labels_last_timing(double* ms5) {
+  if (!ms5) {
+    set_error("fs_pair_labels_last_timing: NULL output");
+    return FS_EINVAL;
+  }
+  gpu::pair_labels_last_timing(ms5);
   return FS_OK;
 }
 

@@ -154,6 +154,8 @@ struct TestHooks {
   int64_t mdr_labels = 0;      // >= 64: labellings per launch of fs_mdr_scan_labels, taken down to a multiple of 64
   int64_t pair_tiles = 0;      // >= 1: tiles per launch of the pair screen's scan (fs_pairscan.hip)
   int64_t pair_cap = 0;        // >= 1: candidates the pair screen's device buffer holds, 256 (one tile's pairs) at least
+  int64_t pair_labels = 0;     // >= 64: labellings per launch of fs_pair_screen_labels, taken down to a multiple of 64
+  int64_t pair_lab_ranks = 0;  // >= 1: pair ranks per launch of fs_pair_screen_labels (fs_pairscan_labels.hip)
 };
 TestHooks& test_hooks();
 

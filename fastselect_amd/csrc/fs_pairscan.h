@@ -145,10 +145,36 @@ int pair_check(int backend, const uint8_t* codes, const uint8_t* ycodes, int64_t
                int n_states, int unit, int score_kind, int64_t n_top, const double* relevance,
                const double* top_score, const int64_t* top_i, const int64_t* top_j);
 
+// ---- fs_pair_screen_labels: the best pair of many labellings of y ----------
+//
+// Row b of the result is (top_score[0], top_i[0], top_j[0]) and the relevance
+// of fs_pair_screen(codes, labels[b], n_top = 1) on the same backend, bit for
+// bit.  Classes.  The class count C of a batch is the largest code over all
+// rows plus one.  A class that a row does not take adds exact zeros to that
+// row's tables: mi_pxy(0) = 0.0, p1 + 0.0 = p1, the class's p2 is 0.0 and
+// used2 counts p2 > 0 only, mi_term(0.0, ., .) = 0.0 and sum + 0.0 = sum.  So
+// a kernel may give every row C classes where a single call gives the row its
+// own count, and the bits are the same (the argument fs_jmi.h makes for the
+// states of a column).
+constexpr int kPairMaxLabelings = 65535;
+
+// Argument checks shared by both backends; they read no array.
+int pair_labels_check(int backend, const uint8_t* codes, const uint8_t* labels,
+                      int64_t n_labelings, int64_t n, int64_t p, int n_states, int unit,
+                      int score_kind, const double* best_score, const int64_t* best_i,
+                      const int64_t* best_j);
+// C of the batch; FS_EINVAL for a label code >= n_states.
+int pair_labels_classes(const uint8_t* labels, int64_t n_labelings, int64_t n, int n_states,
+                        int& C);
+
 namespace cpu {
 int pair_screen(const uint8_t* codes, const uint8_t* ycodes, int64_t n, int64_t p, int n_states,
                 int unit, int score_kind, int n_top, int n_jobs, double* relevance,
                 double* top_score, int64_t* top_i, int64_t* top_j, double* feature_best);
+// relevance: NULL or [n_labelings][p]
+int pair_screen_labels(const uint8_t* codes, const uint8_t* labels, int n_labelings, int64_t n,
+                       int64_t p, int n_states, int unit, int score_kind, int n_jobs,
+                       double* best_score, int64_t* best_i, int64_t* best_j, double* relevance);
 }
 namespace gpu {
 // What the GPU backend refuses without a device: FS_EOOM when the bit-planes of
@@ -162,6 +188,40 @@ int pair_screen(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t
 // relevance, scan with the selection, download (HIP events on the call's
 // stream; the scan phase includes the host merges between its launches).
 void pair_last_timing(double* ms5);
+// fs_pairscan_labels.hip.  pair_labels_limits: FS_EOOM on the sizes alone,
+// then FS_EINVAL for a label code >= n_states or more than kJmiMaxClassesGpu
+// classes over all rows; needs no device.  `classes`: the class count of the
+// batch, which pair_screen_labels takes back (the labels are read once).
+int pair_labels_limits(const uint8_t* labels, int n_labelings, int64_t n, int64_t p, int n_states,
+                       int* classes);
+int pair_screen_labels(int device, const uint8_t* codes, const uint8_t* labels, int n_labelings,
+                       int classes, int64_t n, int64_t p, int n_states, int unit, int score_kind,
+                       double* best_score, int64_t* best_i, int64_t* best_j, double* relevance);
+// Milliseconds of the calling thread's last GPU pair_screen_labels: upload,
+// pack, relevance, scan with the reduction, download.
+void pair_labels_last_timing(double* ms5);
+#if defined(__HIPCC__)
+// The general route of pair_screen_labels (more than 4 states): one labelling
+// through pair_screen's own relevance kernel and scan on planes the caller
+// packed (fs_pairscan.hip).  `y` (device, n codes) is packed into column p
+// first; best: the labelling's first pair under pair_beats.
+struct DevArena;
+struct MiPlanes;
+struct PairScanBufs {
+  double* rel = nullptr;          // p
+  PairCand* cand = nullptr;       // cap
+  unsigned int* cursor = nullptr; // 1
+  int64_t cap = 0;
+  std::vector<PairCand> host;     // cap
+};
+int pair_scan_geometry(MiPlanes& pl, const char* who, int64_t n, int64_t p, int n_states, int& T,
+                       int& CPW);
+int pair_scan_bufs(DevArena& mem, int64_t p, int n_top, PairScanBufs& b);
+int pair_repack_y(const MiPlanes& pl, const uint8_t* y, hipStream_t s);
+int pair_rel_launch(const MiPlanes& pl, int CPW, int unit, double* drel, hipStream_t s);
+int pair_scan_planes(const MiPlanes& pl, int C, int T, int unit, int score_kind, int n_top,
+                     unsigned long long* dfb, PairScanBufs& b, PairTopN& top, hipStream_t s);
+#endif
 }
 
 }  // namespace fs

@@ -344,14 +344,19 @@ void pair_last_timing(double* ms5) {
   for (int k = 0; k < 5; k++) ms5[k] = g_pair_ms[k];
 }
 
-// The geometry of a call and y's classes: FS_EOOM on the sizes alone, before
-// any array is read, then FS_EINVAL for the classes.  Needs no device.
-static int pair_plan(MiPlanes& pl, const uint8_t* ycodes, int64_t n, int64_t p, int n_states,
-                     int& T, int& CPW, int& C) {
+// The geometry of a call: FS_EOOM on the sizes alone, before any array is read.
+int pair_scan_geometry(MiPlanes& pl, const char* who, int64_t n, int64_t p, int n_states, int& T,
+                       int& CPW) {
   const int NB = (n_states + 3) / 4;
   T = 16 / NB;                   // columns of a tile's side
   CPW = kPtThreads / (NB * NB);  // columns per workgroup of k_pair_rel
-  FS_TRY(pl.shape("fs_pair_screen", n, p, n_states, (int)((int64_t)T * CPW / gcd64(T, CPW))));
+  return pl.shape(who, n, p, n_states, (int)((int64_t)T * CPW / gcd64(T, CPW)));
+}
+
+// ... and y's classes: FS_EINVAL.  Needs no device.
+static int pair_plan(MiPlanes& pl, const uint8_t* ycodes, int64_t n, int64_t p, int n_states,
+                     int& T, int& CPW, int& C) {
+  FS_TRY(pair_scan_geometry(pl, "fs_pair_screen", n, p, n_states, T, CPW));
   return pair_y_classes(ycodes, n, n_states, C);
 }
 
@@ -359,6 +364,139 @@ int pair_limits(const uint8_t* ycodes, int64_t n, int64_t p, int n_states) {
   MiPlanes pl;
   int T, CPW, C;
   return pair_plan(pl, ycodes, n, p, n_states, T, CPW, C);
+}
+
+// The relevance, the candidate buffer and its cursor.  The buffer: a test's
+// value, else room for a launch that expects a quarter of it to grow by a
+// factor of two at least; one tile always fits.
+int pair_scan_bufs(DevArena& mem, int64_t p, int n_top, PairScanBufs& b) {
+  int64_t cap = test_hooks().pair_cap > 0 ? test_hooks().pair_cap
+                                          : std::max<int64_t>(16384, 8 * (int64_t)n_top);
+  b.cap = std::min<int64_t>(std::max<int64_t>(cap, kPtThreads), (int64_t)1 << 30);
+  try {
+    b.host.resize((size_t)b.cap);
+  } catch (const std::bad_alloc&) {
+    set_error("fs_pair_screen: out of host memory");
+    return FS_EOOM;
+  }
+  FS_TRY(mem.alloc(&b.rel, (size_t)p));
+  FS_TRY(mem.alloc(&b.cand, (size_t)b.cap));
+  return mem.alloc(&b.cursor, 1);
+}
+
+int pair_rel_launch(const MiPlanes& pl, int CPW, int unit, double* drel, hipStream_t s) {
+  PairRelArgs r;
+  r.row.planes = pl.planes, r.row.kcol = pl.kcol, r.row.n = pl.n, r.row.p = pl.p;
+  r.row.P1p = pl.P1p, r.row.W = pl.W, r.row.SP = pl.SP, r.row.NB = pl.NB, r.row.CPW = CPW;
+  r.row.anchor = pl.p, r.row.anchor_dev = nullptr;  // the target is column p
+  r.unit = unit, r.out = drel;
+  k_pair_rel<<<(unsigned)(pl.P1p / CPW), kPtThreads, 0, s>>>(r);
+  return launch_check("k_pair_rel");
+}
+
+// One thread per word: y (n codes on the device) into column p of packed
+// planes, and its state count into kcol[p] (zeroed by the caller, as
+// MiPlanes::upload does for a whole pack).  The labels were checked on the
+// host.
+__global__ __launch_bounds__(256) void k_pair_repack_y(const uint8_t* __restrict__ y, int64_t n,
+                                                       int64_t p, int64_t P1p, int SP, int64_t W,
+                                                       uint32_t* __restrict__ planes,
+                                                       int32_t* __restrict__ kcol) {
+  const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (w >= W) return;
+  uint32_t code[32];
+  uint32_t mx = 0;
+#pragma unroll
+  for (int b = 0; b < 32; b++) {
+    const int64_t i = w * 32 + b;
+    uint32_t g = 0xffffffffu;  // padding: matches no state
+    if (i < n) {
+      g = y[i];
+      mx = g > mx ? g : mx;
+    }
+    code[b] = g;
+  }
+  uint32_t* out = planes + ((size_t)w * P1p + p) * SP;
+  for (int s = 0; s < SP; s++) {
+    uint32_t word = 0;
+#pragma unroll
+    for (int b = 0; b < 32; b++) word |= (uint32_t)(code[b] == (uint32_t)s) << b;
+    out[s] = word;
+  }
+  atomicMax(&kcol[p], (int32_t)mx + 1);
+}
+
+int pair_repack_y(const MiPlanes& pl, const uint8_t* y, hipStream_t s) {
+  FS_HIP(hipMemsetAsync(pl.kcol + pl.p, 0, 4, s));
+  k_pair_repack_y<<<(unsigned)((pl.W + 255) / 256), 256, 0, s>>>(y, pl.n, pl.p, pl.P1p, pl.SP,
+                                                                 pl.W, pl.planes, pl.kcol);
+  return launch_check("k_pair_repack_y");
+}
+
+// The scan of packed planes with the selection (the head of this file): the
+// n_top best pairs into `top`.  C: the classes of column p, 2..4.
+int pair_scan_planes(const MiPlanes& pl, int C, int T, int unit, int score_kind, int n_top,
+                     unsigned long long* dfb, PairScanBufs& b, PairTopN& top, hipStream_t s) {
+  const int64_t cap = b.cap;
+  std::vector<PairCand>& hc = b.host;
+  PairCand* dcand = b.cand;
+  unsigned int* dcur = b.cursor;
+  PairScanArgs a;
+  a.planes = pl.planes, a.kcol = pl.kcol, a.n = pl.n, a.p = pl.p, a.P1p = pl.P1p, a.W = pl.W;
+  a.SP = pl.SP, a.NB = pl.NB, a.T = T, a.nbf = (pl.p + T - 1) / T;
+  a.unit = unit, a.score_kind = score_kind, a.rel = b.rel, a.fbest = dfb;
+  a.cand = dcand, a.cursor = dcur, a.cap = (unsigned int)cap;
+  const int64_t tiles = a.nbf * (a.nbf + 1) / 2;
+  // a launch of about 2e11 lane operations at most (k_mi_scan's bound, times
+  // the classes), so that no launch holds the device for long
+  const double ops = 256.0 * 32.0 * C * (double)pl.W;
+  const int64_t per_max =
+      std::min<int64_t>(kPairMaxTiles, (int64_t)std::max(1024.0, std::min(2e11 / ops, 1e9)));
+  const int64_t hook_tiles = test_hooks().pair_tiles;
+  std::vector<std::pair<int64_t, int64_t>> todo;  // (first tile, tiles) still to run
+  for (int64_t t0 = 0; t0 < tiles;) {
+    int64_t per;
+    if (hook_tiles > 0)
+      per = std::min(hook_tiles, kPairMaxTiles);
+    else if (!top.full)
+      per = std::min(per_max, cap / (T * T));  // every pair is a candidate: T^2 a tile
+    else
+      per = (int64_t)std::min((double)per_max, (double)t0 * (double)cap / (4.0 * n_top));
+    per = std::min(std::max<int64_t>(per, 1), tiles - t0);
+    todo.assign(1, {t0, per});
+    while (!todo.empty()) {
+      const int64_t b0 = todo.back().first, cnt = todo.back().second;
+      todo.pop_back();
+      a.t0 = b0, a.thr_key = top.thr.key, a.thr_rank = top.thr.rank;
+      FS_HIP(hipMemsetAsync(dcur, 0, 4, s));
+      switch (C) {
+        case 2: k_pair_scan<2><<<(unsigned)cnt, kPtThreads, 0, s>>>(a); break;
+        case 3: k_pair_scan<3><<<(unsigned)cnt, kPtThreads, 0, s>>>(a); break;
+        default: k_pair_scan<4><<<(unsigned)cnt, kPtThreads, 0, s>>>(a); break;
+      }
+      FS_TRY(launch_check("k_pair_scan"));
+      unsigned int got = 0;
+      FS_HIP(hipMemcpyAsync(&got, dcur, 4, hipMemcpyDeviceToHost, s));
+      FS_HIP(hipStreamSynchronize(s));
+      if ((int64_t)got > cap) {
+        // cnt >= 2: one tile yields at most kPtThreads <= cap candidates.
+        // The halves run in ascending order; what this launch did to the
+        // per-feature maxima is a maximum and stands.
+        todo.push_back({b0 + cnt / 2, cnt - cnt / 2});
+        todo.push_back({b0, cnt / 2});
+        continue;
+      }
+      if (got) {
+        FS_HIP(hipMemcpyAsync(hc.data(), dcand, (size_t)got * sizeof(PairCand),
+                              hipMemcpyDeviceToHost, s));
+        FS_HIP(hipStreamSynchronize(s));
+        for (unsigned int t = 0; t < got; t++) top.push(hc[t].key, hc[t].rank);
+        top.compact();
+      }
+    }
+    t0 += per;
+  }
+  return FS_OK;
 }
 
 int pair_screen(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t n, int64_t p,
@@ -370,17 +508,10 @@ int pair_screen(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t
   int T = 0, CPW = 0, C = 0;
   FS_TRY(pair_plan(pl, ycodes, n, p, n_states, T, CPW, C));
   const int64_t total = pair_count(p);
-  // the candidate buffer: a test's value, else room for a launch that expects
-  // a quarter of it to grow by a factor of two at least; one tile always fits
-  int64_t cap = test_hooks().pair_cap > 0 ? test_hooks().pair_cap
-                                          : std::max<int64_t>(16384, 8 * (int64_t)n_top);
-  cap = std::min<int64_t>(std::max<int64_t>(cap, kPtThreads), (int64_t)1 << 30);
 
   PairTopN top((size_t)n_top);
-  std::vector<PairCand> hc;
   std::vector<unsigned long long> hfb;
   try {
-    hc.resize((size_t)cap);
     if (feature_best) hfb.resize((size_t)p);
   } catch (const std::bad_alloc&) {
     set_error("fs_pair_screen: out of host memory");
@@ -393,16 +524,13 @@ int pair_screen(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t
   FS_TRY(lease.open(6));
   hipStream_t s = lease.s;
   std::vector<hipEvent_t>& ev = lease.ev;
-  double* drel = nullptr;
+  PairScanBufs bufs;
   unsigned long long* dfb = nullptr;
-  PairCand* dcand = nullptr;
-  unsigned int* dcur = nullptr;
   // every block is allocated before any array is uploaded
   FS_TRY(pl.alloc(mem, mem));
-  FS_TRY(mem.alloc(&drel, (size_t)p));
   if (feature_best) FS_TRY(mem.alloc(&dfb, (size_t)p));
-  FS_TRY(mem.alloc(&dcand, (size_t)cap));
-  FS_TRY(mem.alloc(&dcur, 1));
+  FS_TRY(pair_scan_bufs(mem, p, n_top, bufs));
+  double* drel = bufs.rel;
 
   FS_HIP(hipEventRecord(ev[0], s));
   FS_TRY(pl.upload(codes, ycodes, s));
@@ -410,15 +538,7 @@ int pair_screen(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t
   FS_HIP(hipEventRecord(ev[1], s));
   FS_TRY(pl.pack(s));
   FS_HIP(hipEventRecord(ev[2], s));
-  {
-    PairRelArgs r;
-    r.row.planes = pl.planes, r.row.kcol = pl.kcol, r.row.n = pl.n, r.row.p = pl.p;
-    r.row.P1p = pl.P1p, r.row.W = pl.W, r.row.SP = pl.SP, r.row.NB = pl.NB, r.row.CPW = CPW;
-    r.row.anchor = pl.p, r.row.anchor_dev = nullptr;  // the target is column p
-    r.unit = unit, r.out = drel;
-    k_pair_rel<<<(unsigned)(pl.P1p / CPW), kPtThreads, 0, s>>>(r);
-    FS_TRY(launch_check("k_pair_rel"));
-  }
+  FS_TRY(pair_rel_launch(pl, CPW, unit, drel, s));
   FS_HIP(hipEventRecord(ev[3], s));
   // the codes are checked before the scan reads a state count
   FS_TRY(pl.fetch_bad(s));
@@ -426,61 +546,7 @@ int pair_screen(int device, const uint8_t* codes, const uint8_t* ycodes, int64_t
   FS_TRY(pl.check());
 
   if (C >= 2) {
-    PairScanArgs a;
-    a.planes = pl.planes, a.kcol = pl.kcol, a.n = n, a.p = p, a.P1p = pl.P1p, a.W = pl.W;
-    a.SP = pl.SP, a.NB = pl.NB, a.T = T, a.nbf = (p + T - 1) / T;
-    a.unit = unit, a.score_kind = score_kind, a.rel = drel, a.fbest = dfb;
-    a.cand = dcand, a.cursor = dcur, a.cap = (unsigned int)cap;
-    const int64_t tiles = a.nbf * (a.nbf + 1) / 2;
-    // a launch of about 2e11 lane operations at most (k_mi_scan's bound, times
-    // the classes), so that no launch holds the device for long
-    const double ops = 256.0 * 32.0 * C * (double)pl.W;
-    const int64_t per_max =
-        std::min<int64_t>(kPairMaxTiles, (int64_t)std::max(1024.0, std::min(2e11 / ops, 1e9)));
-    const int64_t hook_tiles = test_hooks().pair_tiles;
-    std::vector<std::pair<int64_t, int64_t>> todo;  // (first tile, tiles) still to run
-    for (int64_t t0 = 0; t0 < tiles;) {
-      int64_t per;
-      if (hook_tiles > 0)
-        per = std::min(hook_tiles, kPairMaxTiles);
-      else if (!top.full)
-        per = std::min(per_max, cap / (T * T));  // every pair is a candidate: T^2 a tile
-      else
-        per = (int64_t)std::min((double)per_max, (double)t0 * (double)cap / (4.0 * n_top));
-      per = std::min(std::max<int64_t>(per, 1), tiles - t0);
-      todo.assign(1, {t0, per});
-      while (!todo.empty()) {
-        const int64_t b0 = todo.back().first, cnt = todo.back().second;
-        todo.pop_back();
-        a.t0 = b0, a.thr_key = top.thr.key, a.thr_rank = top.thr.rank;
-        FS_HIP(hipMemsetAsync(dcur, 0, 4, s));
-        switch (C) {
-          case 2: k_pair_scan<2><<<(unsigned)cnt, kPtThreads, 0, s>>>(a); break;
-          case 3: k_pair_scan<3><<<(unsigned)cnt, kPtThreads, 0, s>>>(a); break;
-          default: k_pair_scan<4><<<(unsigned)cnt, kPtThreads, 0, s>>>(a); break;
-        }
-        FS_TRY(launch_check("k_pair_scan"));
-        unsigned int got = 0;
-        FS_HIP(hipMemcpyAsync(&got, dcur, 4, hipMemcpyDeviceToHost, s));
-        FS_HIP(hipStreamSynchronize(s));
-        if ((int64_t)got > cap) {
-          // cnt >= 2: one tile yields at most kPtThreads <= cap candidates.
-          // The halves run in ascending order; what this launch did to the
-          // per-feature maxima is a maximum and stands.
-          todo.push_back({b0 + cnt / 2, cnt - cnt / 2});
-          todo.push_back({b0, cnt / 2});
-          continue;
-        }
-        if (got) {
-          FS_HIP(hipMemcpyAsync(hc.data(), dcand, (size_t)got * sizeof(PairCand),
-                                hipMemcpyDeviceToHost, s));
-          FS_HIP(hipStreamSynchronize(s));
-          for (unsigned int t = 0; t < got; t++) top.push(hc[t].key, hc[t].rank);
-          top.compact();
-        }
-      }
-      t0 += per;
-    }
+    FS_TRY(pair_scan_planes(pl, C, T, unit, score_kind, n_top, dfb, bufs, top, s));
   } else {
     // a one-class y: every J and every relevance is exactly 0.0, so is either
     // score; no scan.  The list is the first ranks.

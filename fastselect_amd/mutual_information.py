@@ -168,3 +168,29 @@ def rank_pair_interactions(X, y, n_top=100, *, score="gain", backend="auto", uni
     rel, top_s, top_p, best = _lib.pair_screen(where, X_d, y_d, max_state, n_top=n_top, score=score,
                                                unit=unit, n_jobs=n_jobs, device=device)
     return top_p, top_s, rel, best
+
+
+def pair_screen_null(X, labels, *, score="gain", backend="auto", unit="bit", n_jobs=-1, device=0):
+    """The best pair of ``rank_pair_interactions(X, labels[b], n_top=1)`` for
+    every row b of integer-coded ``labels`` (B x n) in one pass
+    (``fs_pair_screen_labels``): several traits at once, or the null of a
+    caller's own permutation scheme.  The rows are arbitrary.
+
+    Returns (best_pairs int64 [B, 2] with i < j, best_scores float64 [B],
+    relevance float64 [B, p]).  Not a reference function."""
+    X = np.asarray(X)
+    labels = np.asarray(labels)
+    if X.ndim != 2 or labels.ndim != 2 or X.shape[0] != labels.shape[1]:
+        raise ValueError("X must be 2‑D and labels 2‑D with one column per sample")
+    X_d = _validate_discrete(X, "X")
+    l_d = _validate_discrete(labels, "labels")
+    if X.shape[1] < 2:
+        raise ValueError("X must have at least two columns")
+    if not (1 <= labels.shape[0] <= _lib.PAIR_MAX_LABELINGS):
+        raise ValueError(f"labels must have 1..{_lib.PAIR_MAX_LABELINGS} rows")
+    max_state = int(max(X_d.max(), l_d.max())) + 1
+    where = _choose_backend_joint(backend, max_state, int(l_d.max()) + 1)
+    best_s, best_p, rel = _lib.pair_screen_labels(where, X_d, l_d, max_state, score=score,
+                                                  unit=unit, n_jobs=n_jobs, device=device,
+                                                  want_relevance=True)
+    return best_p, best_s, rel

@@ -118,7 +118,8 @@ FS_API int fs_get_accumulation(void);
  * "rf_xlds", "rf_fcap", "ties_1w", "ties_coop", "rf_ref_replay", "ref_q16", "surf_f64",
  * "colsort_bins12", "colsort_global", "star_split", "colsort_star", "mi_tiles",
  * "list_cap", "cfs_rows_cap", "seg_len", "pass2_generic", "mdr_top_cap",
- * "mdr_ranks", "mdr_blocks", "mdr_labels", "pair_tiles", "pair_cap").  FS_EINVAL for an unknown name.
+ * "mdr_ranks", "mdr_blocks", "mdr_labels", "pair_tiles", "pair_cap", "pair_labels",
+ * "pair_lab_ranks").  FS_EINVAL for an unknown name.
  * Not thread-safe against concurrent scoring calls.
  */
 FS_API int fs_test_hook(const char* name, int64_t value);
@@ -835,6 +836,43 @@ FS_API int fs_pair_screen(int backend, int device, const uint8_t* codes, const u
  * merges between them) and download (HIP events; -1 where unavailable), for
  * the benchmark tool. */
 FS_API int fs_pair_screen_last_timing(double* ms5);
+
+/*
+ * The pair screen under many labellings of y in one pass: the null of a
+ * permutation test, or several traits at once.  A pair's joint cells do not
+ * depend on y, so the columns are packed and combined once for all rows.
+ *   labels      [n_labelings][n] row-major codes in 0..n_states-1; the rows are
+ *               arbitrary (they need not be permutations of each other)
+ *   best_score, best_i, best_j  [n_labelings]
+ *   relevance   NULL, or [n_labelings][p]
+ * Row b of best_* is top_score[0], top_i[0], top_j[0] of
+ * fs_pair_screen(codes, labels[b], ..., n_top = 1) on the same backend, bit for
+ * bit: the best pair by (score descending, rank ascending), -0.0 returned as
+ * +0.0; row b of relevance is that call's relevance.  Neither depends on
+ * n_jobs, the launch split or how the labellings are chunked.  A one-class row
+ * gives (0.0, 0, 1) and zero relevance, as fs_pair_screen does.
+ * Classes: the class count of the batch is the largest code over all rows plus
+ * one.  A class that a row does not take adds exact zeros to that row's sums
+ * (its cells' pxy are 0.0, its marginal is 0.0 and is not counted as used, its
+ * terms are 0.0), so the common count changes no bits against the row's own.
+ * FS_EINVAL: as fs_pair_screen (without n_top), and n_labelings outside
+ * 1..65535, NULL labels / best_score / best_i / best_j, a label code >=
+ * n_states; on the GPU backend more than 32 states or more than 4 classes over
+ * all rows.  FS_EOOM is decided from the sizes before any array is read.
+ * On the GPU up to 4 states take a kernel with one lane per labelling; 5..32
+ * states run fs_pair_screen's kernels once per labelling on columns packed
+ * once (correct, and no faster than that many calls by much).
+ */
+FS_API int fs_pair_screen_labels(int backend, int device, const uint8_t* codes,
+                                 const uint8_t* labels, int n_labelings, int64_t n, int64_t p,
+                                 int n_states, int unit, int score_kind, int n_jobs,
+                                 double* best_score, int64_t* best_i, int64_t* best_j,
+                                 double* relevance);
+/* Milliseconds the calling thread's last GPU fs_pair_screen_labels spent on
+ * upload, pack, relevance, the scan with its reduction and download (HIP
+ * events; -1 where unavailable; above 4 states the per-labelling relevance
+ * launches are timed with the scan), for the benchmark tool. */
+FS_API int fs_pair_labels_last_timing(double* ms5);
 
 #ifdef __cplusplus
 }
