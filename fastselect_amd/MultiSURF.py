@@ -19,6 +19,39 @@ from sklearn.utils.validation import check_is_fitted, validate_data
 from . import _base, _lib
 
 
+def stir_p_values(t, df, pooled_sd):
+    """One-sided p-values P(T_df >= t) of the STIR statistics (scipy's
+    Student t survival function).  Where the pooled deviation
+    (``_lib.stir_statistics_ex``) is zero, t is +inf, -inf or 0 and p is 0, 1
+    or 1 (fs_stir.h): only the last differs from the survival function."""
+    from scipy.stats import t as student_t
+    t = np.asarray(t, dtype=np.float64)
+    p = student_t.sf(t, df)
+    p[(np.asarray(pooled_sd) == 0.0) & (t == 0.0)] = 1.0
+    return p
+
+
+def adjust_p_values(p, method="fdr_bh"):
+    """Multiple-testing adjustment of a p-value vector: 'fdr_bh' (Benjamini
+    and Hochberg's step-up adjusted p-values: p_(i) m / i, made monotone from
+    the largest down, capped at 1), 'bonferroni' (p m, capped at 1) or None
+    (a copy)."""
+    p = np.asarray(p, dtype=np.float64)
+    m = p.size
+    if method is None:
+        return p.copy()
+    if method == "bonferroni":
+        return np.minimum(p * m, 1.0)
+    if method != "fdr_bh":
+        raise ValueError(f"adjust must be 'fdr_bh', 'bonferroni' or None; got {method!r}")
+    order = np.argsort(p, kind="stable")
+    scaled = p[order] * m / np.arange(1, m + 1)
+    scaled = np.minimum.accumulate(scaled[::-1])[::-1]
+    out = np.empty(m, dtype=np.float64)
+    out[order] = np.minimum(scaled, 1.0)
+    return out
+
+
 class MultiSURF(TransformerMixin, BaseEstimator):
     """MI355X-accelerated feature selection with the MultiSURF algorithm.
 
@@ -57,6 +90,30 @@ class MultiSURF(TransformerMixin, BaseEstimator):
         float64 partials: closer to the exact sums than the reference's own
         float32 sums, not equal to them.  Not a reference parameter;
         'reference' runs on one device.
+
+    Significance of the scores (``stir_test``)
+    ------------------------------------------
+    A Relief score has no scale of its own, so ``feature_importances_`` does
+    not say which scores differ from zero.  ``stir_test(X, y)`` scores as
+    ``fit`` does and adds STIR ("STatistical Inference Relief", Le,
+    Urbanowicz, Moore and McKinney, Bioinformatics 35(8), 2019): it pools
+    every (focal sample, near hit) pair and every (focal sample, near miss)
+    pair of the fit -- MultiSURF's own neighbourhoods, a pair that is near
+    from both sides counted twice -- and compares, per feature, the diffs of
+    the two populations with a pooled two-sample t-test, one-sided (misses
+    further apart than hits).  The test treats the pairs as independent
+    draws, which they are not, because every sample occurs in many pairs:
+    this is the published method's approximation, and its p-values are not
+    calibrated on noise features (on pure noise expect some very small ones).
+    Read them as a scale for the scores, not as exact error rates.
+
+    Attributes set by ``stir_test`` beside those of ``fit``:
+    ``stir_t_`` (the t statistic per feature), ``stir_p_values_``
+    (P(T_df >= t)), ``stir_p_adjusted_`` (``adjust``: Benjamini-Hochberg,
+    Bonferroni or none), ``stir_hit_mean_`` / ``stir_miss_mean_`` (mean diff
+    over the near-hit / near-miss pairs), ``stir_df_`` (|H| + |M| - 2),
+    ``stir_n_hit_pairs_`` and ``stir_n_miss_pairs_`` (|H|, |M|).  MultiSURF*
+    (``use_star=True``) has no STIR statistic.
     """
 
     def __init__(
@@ -125,6 +182,49 @@ class MultiSURF(TransformerMixin, BaseEstimator):
             return _lib.multisurf_score(self.effective_backend_, x, y, recip_full,
                                         all_feature_indices, self.use_star, is_discrete,
                                         self.n_jobs, devices=self.devices_)
+
+    def stir_test(self, x: np.ndarray, y: np.ndarray, adjust="fdr_bh"):
+        """Score every feature as ``fit`` does and test each score against
+        zero with STIR (see the class docstring): one resident scoring step
+        (the plan TuRF re-scores through), then one extra pass over its near
+        pairs for the four sums per feature and the float64 epilogue.
+
+        adjust : {'fdr_bh', 'bonferroni', None}
+            Multiple-testing adjustment of ``stir_p_values_`` into
+            ``stir_p_adjusted_`` (None: a copy).
+
+        Sets the attributes ``fit`` sets (``feature_importances_`` are the
+        resident step's scores) and the ``stir_*_`` ones.  The resident job
+        (the one TuRF re-scores through) runs on device 0 with the library's
+        default host threads: ``devices`` and ``n_jobs`` are not honoured here
+        as ``fit`` honours them, and ``devices_`` says so.  MultiSURF* has no
+        STIR definition: ValueError.  ValueError too when the fit has fewer
+        than 2 near-hit or fewer than 2 near-miss pairs."""
+        if adjust not in ("fdr_bh", "bonferroni", None):
+            raise ValueError(f"adjust must be 'fdr_bh', 'bonferroni' or None; got {adjust!r}")
+        if self.use_star:
+            raise ValueError("STIR is defined for MultiSURF's near hits and near misses; "
+                             "MultiSURF* (use_star=True) has no STIR statistic")
+        scorer = _ResidentMultiSURF(self, x, y)
+        try:
+            self.devices_ = [0] if self.effective_backend_ == "gpu" else None
+            # a new plan scores every column: nothing to re-target
+            scorer.active = np.arange(scorer.is_discrete.size, dtype=np.int64)
+            scorer.refit(scorer.active)
+            sums, n_hit, n_miss = scorer.job.stir()
+            sums = sums.cpu().numpy()
+        finally:
+            scorer.close()
+        hit_mean, miss_mean, t, df, sp = _lib.stir_statistics_ex(sums, n_hit, n_miss)
+        self.stir_t_ = t
+        self.stir_df_ = df
+        self.stir_hit_mean_ = hit_mean
+        self.stir_miss_mean_ = miss_mean
+        self.stir_n_hit_pairs_ = int(n_hit)
+        self.stir_n_miss_pairs_ = int(n_miss)
+        self.stir_p_values_ = stir_p_values(t, df, sp)
+        self.stir_p_adjusted_ = adjust_p_values(self.stir_p_values_, adjust)
+        return self
 
     def _resident_scorer(self, x, y):
         """A scorer for TuRF that keeps X resident (on the GPU for the GPU

@@ -58,6 +58,7 @@ EXPORTED = (
     "fs_jmi_select", "fs_jmi_rows", "fs_jmi_search_matrix", "fs_jmi_last_timing",
     "fs_pair_screen", "fs_pair_screen_last_timing",
     "fs_pair_screen_labels", "fs_pair_labels_last_timing",
+    "fs_plan_stir", "fs_stir_statistics", "fs_stir_statistics_ex", "fs_plan_stir_kernel_ms",
 )
 
 
@@ -145,6 +146,12 @@ def _load() -> ctypes.CDLL:
     lib.fs_plan_pass1.argtypes = [_vp, _vp]
     lib.fs_plan_select.argtypes = [_vp, _vp, _vp]
     lib.fs_plan_pass2.argtypes = [_vp, _vp, _vp]
+    lib.fs_plan_stir.argtypes = [_vp, _vp]
+    lib.fs_stir_statistics.argtypes = [_f64p, _i64, ctypes.c_double, ctypes.c_double, _f64p,
+                                       _f64p, _f64p, ctypes.POINTER(ctypes.c_double)]
+    lib.fs_stir_statistics_ex.argtypes = list(lib.fs_stir_statistics.argtypes) + [_f64p]
+    lib.fs_plan_stir_kernel_ms.argtypes = [_vp, _int]
+    lib.fs_plan_stir_kernel_ms.restype = ctypes.c_double
     lib.fs_plan_decision_guard.argtypes = [_vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double),
                                            ctypes.POINTER(_int)]
     lib.fs_plan_ref_mask_words.argtypes = [_vp, _i64p]
@@ -233,7 +240,7 @@ def _load() -> ctypes.CDLL:
                  "fs_plan_ref_pass2", "fs_plan_ref_sums", "fs_plan_ref_temp", "fs_plan_info", "fs_plan_set_shard", "fs_multisurf_shards", "fs_plan_calibration", "fs_plan_weighted_pairs",
                  "fs_plan_destroy", "fs_multisurf_score_devices", "fs_relieff_score_devices",
                  "fs_surf_score_devices", "fs_multisurf_score_ex", "fs_relieff_score_ex",
-                 "fs_surf_score_ex"):
+                 "fs_surf_score_ex", "fs_plan_stir", "fs_stir_statistics", "fs_stir_statistics_ex"):
         getattr(lib, name).restype = _int
     return lib
 
@@ -648,6 +655,16 @@ class Plan:
     def pass2(self, counts_ptr: int, scores_ptr: int) -> None:
         check(_lib.fs_plan_pass2(self._h, _vp(counts_ptr), _vp(scores_ptr)))
 
+    def stir(self, sums_ptr: int) -> None:
+        """This plan's STIR partial sums into sums[4 * n_kept] (``fs_plan_stir``:
+        S1H, S2H, S1M, S2M per kept feature), after ``select``."""
+        check(_lib.fs_plan_stir(self._h, _vp(sums_ptr)))
+
+    def stir_kernel_ms(self, which: int) -> float:
+        """HIP-event time of the last ``stir``'s multiplicity (0) / score (1)
+        kernels over its chunks (``fs_plan_stir_kernel_ms``; -1: unavailable)."""
+        return float(_lib.fs_plan_stir_kernel_ms(self._h, int(which)))
+
     def ref_mask_words(self) -> int:
         """int64 words of the reference-order decision masks (``fs_plan_ref_mask_words``)."""
         w = _i64(0)
@@ -725,6 +742,29 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+def stir_statistics(sums, n_hit_pairs, n_miss_pairs):
+    """The STIR epilogue (``fs_stir_statistics``) on the summed (4, n_kept)
+    float64 sums with |H| and |M|: returns (hit_mean, miss_mean, t, df), the
+    first three float64 arrays of n_kept.  ValueError when |H| < 2 or
+    |M| < 2."""
+    return stir_statistics_ex(sums, n_hit_pairs, n_miss_pairs)[:4]
+
+
+def stir_statistics_ex(sums, n_hit_pairs, n_miss_pairs):
+    """``stir_statistics`` and the pooled deviation sp per feature
+    (``fs_stir_statistics_ex``): (hit_mean, miss_mean, t, df, pooled_sd)."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    if sums.ndim != 2 or sums.shape[0] != 4:
+        raise ValueError(f"sums must have shape (4, n_kept); got {sums.shape}")
+    k = sums.shape[1]
+    hm, mm, t, sp = (np.zeros(k, dtype=np.float64) for _ in range(4))
+    df = ctypes.c_double(0.0)
+    check(_lib.fs_stir_statistics_ex(_p(sums, _f64p), k, float(n_hit_pairs), float(n_miss_pairs),
+                                     _p(hm, _f64p), _p(mm, _f64p), _p(t, _f64p),
+                                     ctypes.byref(df), _p(sp, _f64p)))
+    return hm, mm, t, float(df.value), sp
 
 
 class RowsPlan(Plan):

@@ -14,6 +14,7 @@
 #include "fs_mi.h"
 #include "fs_mrmr.h"
 #include "fs_pairscan.h"
+#include "fs_stir.h"
 
 #include <chrono>
 #include <cstdio>
@@ -170,6 +171,8 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "pair_cap") h.pair_cap = value;
   else if (k == "pair_labels") h.pair_labels = value;
   else if (k == "pair_lab_ranks") h.pair_lab_ranks = value;
+  else if (k == "stir_chunk") h.stir_chunk = value;
+  else if (k == "stir_seg_len") h.stir_seg_len = value;
   else {
     set_error("fs_test_hook: unknown hook '" + k + "'");
     return FS_EINVAL;
@@ -637,6 +640,9 @@ struct fs_plan {
   int rank = 0, world = 1, n_jobs = -1;
   int x_is_f64 = 0;
   int64_t r_lo = 0, r_hi = 0;   // focal rows (MultiSURF: fs_plan_set_rows, else [0, n))
+  // a fs_plan_select has run on the current shard, feature set and distances
+  // (fs_plan_stir reads its decisions); pass1 and every re-targeting clear it
+  bool selected = false;
   Prepared P;
   Prepared P0;                  // as created (all columns): discrete tables for re-targeting
   gpu::Plan* g = nullptr;
@@ -842,6 +848,7 @@ int fs_plan_set_features(fs_plan* pl, const int64_t* feat_idx, int64_t n_kept) {
   P.k_neighbors = O.k_neighbors;
   P.ref_accum = O.ref_accum;  // the plan's mode, fixed at creation
   P.no_q16 = O.ref_accum && O.algo == ALGO_MULTISURF && !test_hooks().ref_q16 ? 1 : 0;
+  pl->selected = false;
   if (gpu) {
     rc = gpu::plan_set_features(pl->g, P);
     if (rc != FS_OK) return rc;
@@ -856,6 +863,7 @@ int fs_plan_pass1(fs_plan* pl, double* rowstats) {
     return FS_EINVAL;
   }
   if (!is_multisurf_plan(pl)) return FS_EINVAL;
+  pl->selected = false;  // the distances are written again, unrefined
   if (pl->g) return gpu::plan_pass1(pl->g, rowstats);
   return cpu::multisurf_pass1(pl->P, pl->xp(), pl->rank, pl->world, pl->n_jobs, pl->st,
                               rowstats);
@@ -867,9 +875,62 @@ int fs_plan_select(fs_plan* pl, const double* rowstats, double* counts) {
     return FS_EINVAL;
   }
   if (!is_multisurf_plan(pl)) return FS_EINVAL;
-  if (pl->g) return gpu::plan_select(pl->g, rowstats, counts);
-  return cpu::multisurf_select(pl->P, pl->xp(), pl->rank, pl->world, rowstats, pl->n_jobs,
-                               pl->st, counts);
+  const int rc = pl->g ? gpu::plan_select(pl->g, rowstats, counts)
+                       : cpu::multisurf_select(pl->P, pl->xp(), pl->rank, pl->world, rowstats,
+                                               pl->n_jobs, pl->st, counts);
+  pl->selected = rc == FS_OK;
+  return rc;
+}
+
+int fs_plan_stir(fs_plan* pl, double* sums) {
+  if (!pl || !sums) {
+    set_error("NULL plan or buffer");
+    return FS_EINVAL;
+  }
+  if (pl->P.algo != ALGO_MULTISURF) {
+    set_error("fs_plan_stir: STIR is defined on MultiSURF plans (not ReliefF / SURF)");
+    return FS_EINVAL;
+  }
+  if (pl->P.use_star) {
+    set_error("fs_plan_stir: MultiSURF* has no STIR definition (its far misses are not pairs of "
+              "the test)");
+    return FS_ENOTSUP;
+  }
+  if (!pl->selected) {
+    set_error("fs_plan_stir: no fs_plan_select on the plan's current shard and feature set "
+              "(run pass1 and select after the last re-targeting)");
+    return FS_EINVAL;
+  }
+  if (pl->g) return gpu::plan_stir(pl->g, sums);
+  return cpu::multisurf_stir(pl->P, (const float*)pl->xp(), pl->st, pl->rank, pl->world,
+                             pl->n_jobs, pl->r_lo, pl->r_hi, sums);
+}
+
+int fs_stir_statistics(const double* sums, int64_t n_kept, double n_hit_pairs,
+                       double n_miss_pairs, double* hit_mean, double* miss_mean, double* t,
+                       double* df) {
+  return fs_stir_statistics_ex(sums, n_kept, n_hit_pairs, n_miss_pairs, hit_mean, miss_mean, t,
+                               df, nullptr);
+}
+
+int fs_stir_statistics_ex(const double* sums, int64_t n_kept, double n_hit_pairs,
+                          double n_miss_pairs, double* hit_mean, double* miss_mean, double* t,
+                          double* df, double* pooled_sd) {
+  if (n_kept < 0 || (n_kept > 0 && !sums)) {
+    set_error("fs_stir_statistics: NULL sums or n_kept < 0");
+    return FS_EINVAL;
+  }
+  if (!stir::statistics(sums, n_kept, n_hit_pairs, n_miss_pairs, hit_mean, miss_mean, t, df,
+                        pooled_sd)) {
+    set_error("fs_stir_statistics: fewer than 2 near-hit pairs or fewer than 2 near-miss pairs");
+    return FS_EINVAL;
+  }
+  return FS_OK;
+}
+
+double fs_plan_stir_kernel_ms(const fs_plan* pl, int which) {
+  if (!pl || !pl->g) return -1.0;
+  return gpu::plan_stir_kernel_ms(pl->g, which);
 }
 
 int fs_plan_pass2(fs_plan* pl, const double* counts, double* scores) {
@@ -968,7 +1029,9 @@ int fs_plan_decision_guard(fs_plan* pl, const double* rowstats, const double* co
   *switched_out = 0;
   // the CPU backend always runs pass 1 on 32-bit operands
   if (!pl->g) return FS_OK;
-  return gpu::plan_decision_guard(pl->g, rowstats, counts, scores, risk_out, switched_out);
+  const int rc = gpu::plan_decision_guard(pl->g, rowstats, counts, scores, risk_out, switched_out);
+  if (rc != FS_OK || *switched_out) pl->selected = false;  // a new layout: the step runs again
+  return rc;
 }
 
 int fs_plan_set_rows(fs_plan* pl, int64_t row_begin, int64_t row_end) {
@@ -1005,6 +1068,7 @@ int fs_plan_set_shard(fs_plan* pl, int rank, int world) {
               "fs_plan_ref_pass2) runs on the GPU backend only");
     return FS_ENOTSUP;
   }
+  pl->selected = false;
   if (pl->g) {
     const int rc = gpu::plan_set_shard(pl->g, rank, world);
     if (rc != FS_OK) return rc;

@@ -14,6 +14,7 @@
 //   fs_relieff.hip   ReliefF selection and update
 //   fs_plan.hip      plan create / layout / shard / score entry points
 //   fs_devices.hip   single-process multi-GPU (the estimators' devices=)
+//   fs_stir.hip      STIR: hit / miss sums of diff and diff^2 over the near pairs
 //
 // Kernel map and rooflines: DESIGN.md §3.  No float atomics touch scores:
 // every reduction has a fixed order, so two runs of the same input are
@@ -138,7 +139,7 @@ __device__ __forceinline__ int64_t d_rd(int tiled, int2 win, int64_t n_pad, int6
 // live and die together sit in one of four arenas, named at each allocation:
 // mem_plan (sized by n: as long as the plan), mem_layout (sized by the feature
 // layout: until the next plan_layout), mem_shard (sized by the owned tiles:
-// until the next plan_set_shard) and mem_call (one plan_score call).  A buffer
+// until the next plan_set_shard) and mem_call (one plan_score or plan_stir call).  A buffer
 // that grows on demand is a DevBuf member: reserve() synchronises the streams
 // it is given, frees the old block and allocates the new size.  Kernels take
 // the raw pointer (.p) and capacity (.cap).  plan_destroy synchronises the
@@ -239,10 +240,14 @@ struct Plan {
   // ev[0..1] distance kernel, ev[2..3] score kernel(s) / ReliefF selection +
   // update, ev[4..5] ReliefF's first k_rf_select launch (plan_kernel_ms)
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // plan_stir (fs_stir.hip): per chunk of tiles the weights kernel's and the
+  // score kernel's start / stop events (plan_stir_kernel_ms), taken on demand
+  std::vector<hipEvent_t> ev_stir;
+  int stir_chunks = 0;          // chunks the last plan_stir walked
   DevArena mem_plan{device};    // buffers sized by n (live as long as the plan)
   DevArena mem_layout{device};  // buffers sized by the feature layout (PW)
   DevArena mem_shard{device};   // buffers sized by the owned tiles (plan_set_shard)
-  DevArena mem_call{device};    // buffers of one plan_score call
+  DevArena mem_call{device};    // buffers of one plan_score / plan_stir call
   bool row_mode = false;
   // the row guard's quantised operands and mean correction are the first
   // step's (one plan over every continuous column): pass 1 takes them

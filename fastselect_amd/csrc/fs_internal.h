@@ -156,6 +156,8 @@ struct TestHooks {
   int64_t pair_cap = 0;        // >= 1: candidates the pair screen's device buffer holds, 256 (one tile's pairs) at least
   int64_t pair_labels = 0;     // >= 64: labellings per launch of fs_pair_screen_labels, taken down to a multiple of 64
   int64_t pair_lab_ranks = 0;  // >= 1: pair ranks per launch of fs_pair_screen_labels (fs_pairscan_labels.hip)
+  int64_t stir_chunk = 0;      // >= 1: tiles per chunk of plan_stir's per-pair buffer, up to whole segments (fs_stir.hip)
+  int64_t stir_seg_len = 0;    // >= 1: tiles per segment of k_stir_score (plan_stir; small n computes 1)
 };
 TestHooks& test_hooks();
 
@@ -512,6 +514,11 @@ int plan_set_features(Plan* g, const Prepared& P);
 int plan_pass1(Plan* g, double* rowstats_dev);
 int plan_select(Plan* g, const double* rowstats_dev, double* counts_dev);
 int plan_pass2(Plan* g, const double* counts_dev, double* scores_dev);
+// STIR (fs_stir.h): the four sums of this plan's near pairs into
+// sums_dev[4 * n_kept], after a plan_select on the current shard and layout;
+// plan_stir_kernel_ms: the last call's weights (0) / score (1) kernel time.
+int plan_stir(Plan* g, double* sums_dev);
+double plan_stir_kernel_ms(const Plan* g, int which);
 int64_t ref_mask_words(const Plan* g);
 int plan_ref_masks(Plan* g, uint64_t* masks_dev);
 int plan_ref_pass2(Plan* g, const uint64_t* masks_dev, const double* counts_dev, int64_t row_lo,

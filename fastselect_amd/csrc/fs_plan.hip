@@ -13,6 +13,7 @@ void plan_destroy(Plan* g) {
   if (g->side2) (void)hipStreamSynchronize(g->side2);
   if (g->x_staged) staged_release(g->x_staged);
   for (auto& e : g->ev) event_put(g->device, e, true);
+  for (auto& e : g->ev_stir) event_put(g->device, e, true);
   event_put(g->device, g->ev_fork, false);
   event_put(g->device, g->ev_join, false);
   event_put(g->device, g->ev_star, false);
@@ -158,6 +159,7 @@ int plan_layout(Plan* g) {
   FS_HIP(hipStreamSynchronize(g->stream));
   if (g->side) FS_HIP(hipStreamSynchronize(g->side));
   if (g->side2) FS_HIP(hipStreamSynchronize(g->side2));
+  g->mem_call.release();  // a plan_stir's buffers on a caller's stream
   g->mem_layout.release();
   int rc;
   Q.q16 = g->use_q16;
@@ -337,6 +339,7 @@ int plan_set_shard(Plan* g, int rank, int world) {
   FS_HIP(hipStreamSynchronize(g->stream));
   if (g->side) FS_HIP(hipStreamSynchronize(g->side));
   if (g->side2) FS_HIP(hipStreamSynchronize(g->side2));
+  g->mem_call.release();  // a plan_stir's buffers on a caller's stream
   g->mem_shard.release();
   g->D = g->Dpart = nullptr;
   g->D_alloc = nullptr;

@@ -211,6 +211,8 @@ class ShardedMultiSURF:
             self.plan = _lib.Plan(backend, x, y, recip, is_discrete, use_star=use_star,
                                   rank=self.rank, world=self.world * self.shards, device=device,
                                   stream=stream)
+        self.rows = None if rows is None else (int(rows[0]), int(rows[1]))
+        self._stepped = False  # a step() has run on the current feature set (stir)
         if rows is not None:  # focal-sample slice: pass 2 sums those samples only
             self.plan.set_rows(*rows)
         if self.ref_chain:
@@ -259,6 +261,7 @@ class ShardedMultiSURF:
         """Score another feature subset of the resident samples from the next
         step on (fs_plan_set_features: X stays on the device)."""
         import torch
+        self._stepped = False  # stir() needs a step() on the new feature set
         with self._on_stream():
             self.plan.set_features(feat_idx)
             n_kept = self.plan.n_kept
@@ -416,7 +419,46 @@ class ShardedMultiSURF:
             import torch
             s.record_stream(torch.cuda.current_stream(self.tdev))
         self.last_guard = (risk, switched)
+        self._stepped = True
         return s
+
+    def stir(self):
+        """The STIR sums of the last ``step()`` (``fs_plan_stir``; DESIGN.md
+        §STIR): returns ``(sums, n_hit_pairs, n_miss_pairs)`` -- the (4, n_kept)
+        float64 tensor of S1H, S2H, S1M, S2M summed over this job's shards and
+        all-reduced over the ranks, with |H| and |M| from the step's
+        all-reduced neighbour counts (restricted to ``rows`` when the job
+        scores a focal-sample slice; the slices' sums and counts add up).
+        ``_lib.stir_statistics`` turns them into t-statistics.  The plan's
+        pass-2 state is left alone: the next ``step()`` returns the bits it
+        would have returned.  With V > 1 tile shards it runs a round of its
+        own over the shards (distances and decisions recomputed per shard, as
+        the step's rounds do)."""
+        import torch
+        if not self._stepped:
+            raise ValueError("stir() follows a step() on the current feature set: it reads the "
+                             "step's thresholds, decisions and counts")
+        with self._on_stream():
+            k = self.plan.n_kept
+            sums = torch.zeros(4 * k, dtype=torch.float64, device=self.tdev)
+            if self.shards > 1:
+                tmp3 = torch.zeros_like(self.rowstats)
+                tmp2 = torch.zeros_like(self.counts)
+                part = torch.zeros_like(sums)
+                for v in range(self.shards):
+                    self._shard(v)
+                    self.plan.pass1(tmp3.data_ptr())
+                    self.plan.select(self.rowstats.data_ptr(), tmp2.data_ptr())
+                    self.plan.stir(part.data_ptr())
+                    sums += part
+            else:
+                self.plan.stir(sums.data_ptr())
+            self._allreduce(sums)
+            lo, hi = self.rows if self.rows is not None else (0, self.n)
+            c = self.counts.view(self.n, 2)[lo:hi].sum(dim=0).cpu()
+        if self.stream is not None:  # sums is consumed on the caller's stream
+            sums.record_stream(torch.cuda.current_stream(self.tdev))
+        return sums.view(4, k), float(c[0]), float(c[1])
 
     def info(self):
         return self.plan.info()

@@ -119,7 +119,7 @@ FS_API int fs_get_accumulation(void);
  * "colsort_bins12", "colsort_global", "star_split", "colsort_star", "mi_tiles",
  * "list_cap", "cfs_rows_cap", "seg_len", "pass2_generic", "mdr_top_cap",
  * "mdr_ranks", "mdr_blocks", "mdr_labels", "pair_tiles", "pair_cap", "pair_labels",
- * "pair_lab_ranks").  FS_EINVAL for an unknown name.
+ * "pair_lab_ranks", "stir_chunk", "stir_seg_len").  FS_EINVAL for an unknown name.
  * Not thread-safe against concurrent scoring calls.
  */
 FS_API int fs_test_hook(const char* name, int64_t value);
@@ -389,6 +389,58 @@ FS_API int fs_plan_select(fs_plan* plan, const double* rowstats, double* counts)
 /* Stage 3: pair weights from the all-reduced counts[2n]; partial per-feature
  * score sums (NOT divided by n) -> scores[n_kept], in feat_idx order. */
 FS_API int fs_plan_pass2(fs_plan* plan, const double* counts, double* scores);
+/* STIR ("STatistical Inference Relief", Le, Urbanowicz, Moore and McKinney,
+ * Bioinformatics 35(8), 2019): t-statistics for MultiSURF scores from the
+ * near pairs of a fit, without permutations.  H is the multiset of ordered
+ * pairs (i, j) with j in MultiSURF's near set of focal sample i and
+ * y_j == y_i, M the same with y_j != y_i (the plan's own decisions, the ones
+ * pass 2 weighs; a pair near from both sides counts twice); per feature the
+ * diffs over M and over H are compared with a pooled two-sample t-test
+ * (definitions: fastselect_amd/csrc/fs_stir.h).  The test treats the
+ * |H| + |M| pairs as independent, which they are not (every sample occurs in
+ * many pairs): that is the published method's approximation.
+ *
+ * fs_plan_stir: sums[4 * n_kept] in the plan's memory space (device memory
+ * for the GPU backend, host memory for the CPU backend), sums[q * n_kept + k]
+ * with q = 0..3 for S1H, S2H (sum of diff, of diff^2 over H), S1M, S2M, k in
+ * feat_idx order.  Like the score sums of fs_plan_pass2 they are this plan's
+ * partial sums, not normalised: its pairs are those of its owned tiles, and a
+ * side of a pair counts only when its focal sample lies in the
+ * fs_plan_set_rows range.  The partials of all (rank, world) plans, of all
+ * tile shards and of disjoint row ranges add up to the whole.  Needs a
+ * fs_plan_select on the plan's current shard and feature set since the last
+ * re-targeting or pass1 (else FS_EINVAL).  MultiSURF* plans: FS_ENOTSUP (no
+ * STIR definition); ReliefF / SURF plans: FS_EINVAL.  Works in both
+ * accumulation modes (it reads the distances, thresholds and labels only);
+ * enqueued on the plan's stream, the host waits only when the stream is the
+ * plan's own.  Pass 2's state is untouched: the next fs_plan_pass2 returns
+ * the bits it returned before.  The GPU backend sums fixed-point terms
+ * exactly: its error is absolute, 1.2e-7 of the plan's largest scaled feature
+ * range per diff (and of its square per squared diff), so squares below that
+ * count as 0 (fs_stir.h, "Error of the GPU sums").
+ *
+ * fs_stir_statistics: the host epilogue on the summed sums[4 * n_kept] with
+ * |H| = n_hit_pairs (the sum of counts[2i] over the focal rows in use) and
+ * |M| = n_miss_pairs (of counts[2i + 1]): per feature the hit and miss means,
+ * t = (Mbar - Hbar) / (sp sqrt(1/|M| + 1/|H|)) with the pooled deviation sp
+ * (variances clamped at 0; sp == 0: t = +inf, -inf or 0 by the sign of
+ * Mbar - Hbar), and *df = |M| + |H| - 2.  All float64; any output may be
+ * NULL.  The one-sided p-value P(T_df >= t) is left to the caller.
+ * |H| < 2 or |M| < 2: FS_EINVAL. */
+FS_API int fs_plan_stir(fs_plan* plan, double* sums);
+FS_API int fs_stir_statistics(const double* sums, int64_t n_kept, double n_hit_pairs,
+                              double n_miss_pairs, double* hit_mean, double* miss_mean,
+                              double* t, double* df);
+/* The same, and pooled_sd[n_kept] = sp per feature (or NULL): where it is 0,
+ * t is +inf, -inf or 0 by definition and the p-value is 0, 1 or 1 instead of
+ * the t distribution's. */
+FS_API int fs_stir_statistics_ex(const double* sums, int64_t n_kept, double n_hit_pairs,
+                                 double n_miss_pairs, double* hit_mean, double* miss_mean,
+                                 double* t, double* df, double* pooled_sd);
+/* Summed HIP-event time in milliseconds of the last fs_plan_stir's kernels
+ * over its chunks of tiles (GPU only; -1 when unavailable).  which: 0 = the
+ * pair-multiplicity kernel, 1 = the score kernel. */
+FS_API double fs_plan_stir_kernel_ms(const fs_plan* plan, int which);
 /* After the three stages of a MultiSURF step, with rowstats[3n], counts[2n]
  * and scores[n_kept] all-reduced (identical on every rank): the 16-bit
  * decision check of fs_multisurf_score (see fs_multisurf_last_guard) for
