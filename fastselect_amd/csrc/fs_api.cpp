@@ -163,6 +163,7 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "cfs_rows_cap") h.cfs_rows_cap = value;
   else if (k == "seg_len") h.seg_len = value;
   else if (k == "pass2_generic") h.pass2_generic = value;
+  else if (k == "pass2_w8") h.pass2_w8 = value;
   else if (k == "mdr_top_cap") h.mdr_top_cap = value;
   else if (k == "mdr_ranks") h.mdr_ranks = value;
   else if (k == "mdr_blocks") h.mdr_blocks = value;

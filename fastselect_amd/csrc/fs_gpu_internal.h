@@ -220,9 +220,13 @@ struct Plan {
   std::vector<int2> h_tiles;      // the owned tiles (host copy of `tiles`)
   DevBuf<int32_t> sched{device};  // the tile order, then the segment offsets
   int32_t* seg_off = nullptr;     // inside sched
-  DevBuf<int2> units8{device};    // the F = 8 units, then the F = 4 ones
+  DevBuf<int2> units8{device};    // the F = 8 units, then the F = 4 ones, then the 8-wave kernel's
   int2* units4 = nullptr;         // inside units8
+  int2* unitsw = nullptr;         // inside units8
   int64_t nunits8 = 0, nunits4 = 0, nfb8 = 0, nfb4 = 0, f_tail = 0;
+  // k_score_sparse3_w8 (choose_w8): its 256-feature blocks cover features
+  // [0, f_w8), the F = 8 / F = 4 launches the rest
+  int64_t nunitsw = 0, nfbw = 0, f_w8 = 0;
   // exact thresholds of uncertain rows (exact_thresholds)
   unsigned int* unc = nullptr;  // [n_pad] row flags
   int32_t* urows = nullptr;     // [n_pad + 1] flagged rows in index order, then their count
@@ -363,6 +367,7 @@ int star_sums(Plan* g, hipStream_t st, bool continuous);
 int star_reduce(Plan* g, const double* counts, hipStream_t st);
 // fs_pass2.hip
 int shard_segments(Plan* g);
+int choose_w8(int64_t units, double tiles_per_seg);  // fs_plan.hip
 int run_weights(Plan* g, const double* counts, int algo, double inv_sc);
 int run_pass2(Plan* g, double* scores_dev);
 int ref_masks(Plan* g);

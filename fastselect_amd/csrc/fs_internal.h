@@ -148,6 +148,7 @@ struct TestHooks {
   int64_t cfs_rows_cap = 0;    // >= 1: rows the CFS row cache holds at first (fs_cfs.hip)
   int64_t seg_len = 0;         // >= 1: tiles per pass-2 segment (shard_segments; small n computes 1)
   int64_t pass2_generic = 0;   // 1: every k_score_sparse3 unit takes the plain-HIP walk
+  int64_t pass2_w8 = -1;       // 0 / 1: all-continuous blocks on k_score_sparse3 / k_score_sparse3_w8 (choose_w8)
   int64_t mdr_top_cap = 0;     // >= 1: candidates fs_mdr_scan_top's device buffer holds (fs_mdr.hip)
   int64_t mdr_ranks = 0;       // >= 1: ranks per launch of the three MDR scans, no 65536 floor (fs_mdr.hip)
   int64_t mdr_blocks = 0;      // >= 1: blocks (rank runs) per launch of the three MDR scans at most

@@ -522,6 +522,87 @@ __global__ __launch_bounds__(1024) void k_score_sparse3(
   }
 }
 
+// The 8-wave form of the segment walk: 256-feature units (four features per
+// lane), a 64 KB row block with a 1 KB row pitch and at most 64 VGPRs, so two
+// workgroups share a CU and every SIMD holds 8 waves instead of 4 -- a wave
+// parked at a wait has seven partners.  Same streams per wave, same terms,
+// same order and fold points as k_score_sparse3: a feature's partial in spart
+// does not depend on the width of the unit that computed it.  Only units
+// whose real features are all continuous come here (unitsw of
+// build_sparse_schedule: 256-feature blocks f0 = 256 fb from feature 0 on);
+// the generated statement FS_SPARSE3_SEG_ASM_W8 is the only walk (the plain-
+// HIP walk does not fit the register budget and stays with k_score_sparse3).
+__global__ __launch_bounds__(1024, 8) void k_score_sparse3_w8(
+    const float* __restrict__ xs, int64_t PW, const int2* __restrict__ tiles,
+    const float* __restrict__ wrow, const int32_t* __restrict__ sched,
+    const int32_t* __restrict__ seg_off, const int2* __restrict__ units,
+    double* __restrict__ spart) {
+  constexpr int F = 4;
+  __shared__ float4 As[kHalf * 64];  // 64 rows x 64 lanes (64 KB)
+  __shared__ unsigned int wg_done;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int2 unit = units[blockIdx.x];
+  if (unit.x < 0) return;
+  const int64_t seg = unit.x, fb = unit.y >> 1, h = unit.y & 1;
+  const int64_t f0 = fb * (64 * F);
+  const int t_begin = seg_off[seg], t_end = seg_off[seg + 1];
+  const uint32_t lds_lane = (uint32_t)(uintptr_t)As + (uint32_t)lane * 16u;
+  const uint32_t glb_lane = (uint32_t)lane * 16u;
+  const uint32_t bstride_b = (uint32_t)(kSWaves * PW * sizeof(float));
+  double* __restrict__ out = spart + (seg * 2 + h) * PW + f0;
+  int nvalid = (int)(PW - f0 < 64 * F ? PW - f0 : 64 * F);
+  asm volatile("" : "+s"(out), "+s"(nvalid));
+  double s[F] = {0.0, 0.0, 0.0, 0.0};
+  if (threadIdx.x == 0) wg_done = 0u;  // before the staging barrier
+  if (t_begin < t_end) {
+    // the segment's row block, once: 4 rows per wave, all requested before the
+    // first store; lanes past PW stage zeros
+    const int bi = tiles[sched[t_begin]].x;
+    const float* __restrict__ xa = xs + ((int64_t)bi * kTile + h * kHalf + wave) * PW + f0 + 4 * lane;
+    constexpr int kPer = kHalf / kSWaves;
+    float4 v[kPer];
+#pragma unroll
+    for (int m = 0; m < kPer; m++) {
+      v[m] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (f0 + 4 * lane < PW) v[m] = *(const float4*)(xa + (int64_t)(kSWaves * m) * PW);
+    }
+#pragma unroll
+    for (int m = 0; m < kPer; m++) As[(wave + kSWaves * m) * 64 + lane] = v[m];
+    __syncthreads();
+    const uint64_t entw = (uint64_t)(uintptr_t)(wrow + (h * kSWaves + wave) * kStreamWeights);
+    const uint64_t xsw = (uint64_t)(uintptr_t)(xs + (int64_t)wave * PW + f0);
+    const uint32_t entw_lo = (uint32_t)entw, entw_hi = (uint32_t)(entw >> 32);
+    const uint32_t xsw_lo = (uint32_t)xsw, xsw_hi = (uint32_t)(xsw >> 32);
+    const uint32_t wgd = (uint32_t)(uintptr_t)&wg_done;
+    for (int k0 = t_begin; k0 < t_end; k0 += 64) {
+      const uint32_t done0 = (uint32_t)(k0 - t_begin);
+      const int kk = k0 + lane;
+      const int my_t = sched[kk < t_end ? kk : k0];
+      const int my_y = tiles[my_t].y;
+      const uint32_t nt = (uint32_t)(t_end - k0 < 64 ? t_end - k0 : 64);
+      FS_SPARSE3_SEG_ASM_W8(s, lds_lane, glb_lane, my_t, my_y, nt, entw_lo, entw_hi, xsw_lo, xsw_hi,
+                            bstride_b, wgd, done0);
+    }
+  }
+  // fixed-order reduction of the 16 waves' partials through the LDS block
+  __syncthreads();
+  double* red = (double*)As;  // [F][kSWaves][64] (32 KB)
+#pragma unroll
+  for (int q = 0; q < F; q++) red[(q * kSWaves + wave) * 64 + lane] = s[q];
+  __syncthreads();
+  if (wave < F) {
+    const int q = wave;  // feature f0 + 4 lane + q
+    const int f = 4 * lane + q;
+    const double* rr = red + q * kSWaves * 64 + lane;
+    double v = 0.0;
+#pragma unroll
+    for (int w = 0; w < kSWaves; w += 4)
+      v += (rr[w * 64] + rr[(w + 1) * 64]) + (rr[(w + 2) * 64] + rr[(w + 3) * 64]);
+    if (f < nvalid) out[f] = v;
+  }
+}
+
 // dst[k] += src[k] (the tile shards' partial vectors, summed in shard order).
 __global__ void k_accumulate(double* __restrict__ dst, const double* __restrict__ src,
                              int64_t count) {
@@ -598,6 +679,13 @@ int reduce_segments(const double* part, int64_t nrows, int64_t PW, const int64_t
 #endif
 constexpr int kSchedRows = FS_SCHED_ROWS;                 // row blocks per group
 constexpr int kSchedFb = FS_SCHED_UNITS / kSchedRows;  // feature blocks per block of units
+// k_score_sparse3_w8: an XCD holds 64 units at a time (two per CU).  256-
+// feature blocks per block of units: 4 = the feature span and the two rounds
+// of the 512-wide form, 2 = one round (profiles/pass2_w8/ab.txt).
+#ifndef FS_SCHED_FB_W8
+#define FS_SCHED_FB_W8 4
+#endif
+constexpr int kSchedFbW8 = FS_SCHED_FB_W8;
 
 static int build_sparse_schedule(Plan* g) {
   const Prepared& Q = g->P;
@@ -623,19 +711,28 @@ static int build_sparse_schedule(Plan* g) {
   // feature blocks of the two launches (run_pass2): 512-wide, then a tail
   // of <= 256 features in one 256-wide block (a longer tail takes one more,
   // partial, 512-wide block: its cost is mostly its entry walk)
-  g->nfb8 = Q.PW / 512;
-  if (Q.PW - g->nfb8 * 512 > 256) g->nfb8++;
-  g->f_tail = std::min<int64_t>(g->nfb8 * 512, Q.PW);
+  // With the 8-wave kernel (choose_w8) the leading 256-feature blocks whose
+  // real features are all continuous are its units (PC is a multiple of 64:
+  // PC / 256 whole blocks, and the partial last block of an all-continuous
+  // layout); the two launches above cover what is left, from f_w8 on.
+  const int64_t nfb_all = 2 * ((Q.PW + 511) / 512);
+  const int w8 = choose_w8(g->nseg * 2 * nfb_all, (double)T / (double)g->nseg);
+  g->nfbw = !w8 ? 0 : Q.PC == Q.PW ? (Q.PW + 255) / 256 : Q.PC / 256;
+  g->f_w8 = std::min<int64_t>(g->nfbw * 256, Q.PW);
+  const int64_t rest = Q.PW - g->f_w8;
+  g->nfb8 = rest / 512;
+  if (rest - g->nfb8 * 512 > 256) g->nfb8++;
+  g->f_tail = std::min<int64_t>(g->f_w8 + g->nfb8 * 512, Q.PW);
   g->nfb4 = (Q.PW - g->f_tail + 255) / 256;
-  auto units_of = [&](int64_t nfb, std::vector<int2>& table) {
+  auto units_of = [&](int64_t nfb, int64_t kfb, std::vector<int2>& table) {
     std::vector<std::vector<int2>> per(kXcds);
     std::vector<int64_t> load(kXcds, 0);
     for (const auto& gr : groups)
-      for (int64_t f0 = 0; f0 < nfb; f0 += kSchedFb) {
+      for (int64_t f0 = 0; f0 < nfb; f0 += kfb) {
         int x = 0;
         for (int q = 1; q < kXcds; q++)
           if (load[q] < load[x]) x = q;
-        for (int64_t fb = f0; fb < std::min<int64_t>(nfb, f0 + kSchedFb); fb++)
+        for (int64_t fb = f0; fb < std::min<int64_t>(nfb, f0 + kfb); fb++)
           for (int32_t sg : gr.second)
             for (int h = 0; h < 2; h++) {
               per[x].push_back(make_int2(sg, (int)(2 * fb + h)));
@@ -648,22 +745,26 @@ static int build_sparse_schedule(Plan* g) {
     for (int x = 0; x < kXcds; x++)
       for (size_t k = 0; k < per[x].size(); k++) table[x + kXcds * k] = per[x][k];
   };
-  std::vector<int2> u8, u4;
-  units_of(g->nfb8, u8);
-  units_of(g->nfb4, u4);
+  std::vector<int2> u8, u4, uw;
+  units_of(g->nfb8, kSchedFb, u8);
+  units_of(g->nfb4, kSchedFb, u4);
+  units_of(g->nfbw, kSchedFbW8, uw);
   g->nunits8 = (int64_t)u8.size();
   g->nunits4 = (int64_t)u4.size();
+  g->nunitsw = (int64_t)uw.size();
   if (sched.empty()) sched.push_back(0);
   const size_t ns = sched.size() + seg_off.size();
-  const size_t nu = std::max<size_t>(1, u8.size() + u4.size());
+  const size_t nu = std::max<size_t>(1, u8.size() + u4.size() + uw.size());
   FS_TRY(g->sched.reserve(ns, 0, &g->stream, 1));
   FS_TRY(g->units8.reserve(nu, 0, &g->stream, 1));
   g->seg_off = g->sched.p + sched.size();
   g->units4 = g->units8.p + u8.size();
+  g->unitsw = g->units4 + u4.size();
   FS_TRY(h2d(g, g->sched.p, sched.data(), sched.size()));
   FS_TRY(h2d(g, g->seg_off, seg_off.data(), seg_off.size()));
   if (!u8.empty()) FS_TRY(h2d(g, g->units8.p, u8.data(), u8.size()));
   if (!u4.empty()) FS_TRY(h2d(g, g->units4, u4.data(), u4.size()));
+  if (!uw.empty()) FS_TRY(h2d(g, g->unitsw, uw.data(), uw.size()));
   return FS_OK;
 }
 
@@ -756,10 +857,17 @@ int run_pass2(Plan* g, double* scores_dev) {
     // F = 8 block is cheaper than two F = 4 ones -- cfg2, 448 features:
     // 0.24 -> 0.17 ms)
     const int generic = test_hooks().pass2_generic == 1 ? 1 : 0;  // tests: every unit on the plain-HIP walk
+    // the all-continuous 256-feature blocks of an 8-wave plan first, then
+    // what is left from f_w8 on (f_w8 = 0 without)
+    if (g->nunitsw > 0) {
+      k_score_sparse3_w8<<<(unsigned)g->nunitsw, 64 * kSWaves, 0, g->stream>>>(
+          g->xs, Q.PW, g->tiles, g->wrow, g->sched.p, g->seg_off, g->unitsw, g->spart.p);
+      FS_TRY(launch_check("k_score_sparse3_w8"));
+    }
     if (g->nunits8 > 0) {
       k_score_sparse3<8><<<(unsigned)g->nunits8, 64 * kSWaves, 0, g->stream>>>(
-          g->xs, Q.PW, Q.PC, g->tiles, g->wrow, g->sched.p, g->seg_off, g->units8.p, 0, g->spart.p,
-          generic);
+          g->xs, Q.PW, Q.PC, g->tiles, g->wrow, g->sched.p, g->seg_off, g->units8.p, g->f_w8,
+          g->spart.p, generic);
       FS_TRY(launch_check("k_score_sparse3<8>"));
     }
     if (g->nunits4 > 0) {

@@ -93,6 +93,32 @@ static int choose_sparse(const Plan* g, const Prepared& P) {
   return (P.algo == ALGO_SURF && g->r_hi - g->r_lo < P.n) ? 1 : 0;
 }
 
+// All-continuous feature blocks of the sparse pass 2 on the 8-wave kernel
+// (k_score_sparse3_w8: 256-feature units, two workgroups per CU) or on
+// k_score_sparse3 (512-feature units, one per CU).  In plan quantities only:
+// `units` = segments x 2 halves x 256-feature blocks of the layout (the
+// workgroups the 8-wave kernel launches for an all-continuous layout) and the
+// mean tiles per segment.  Same box, alternating with the parent
+// (profiles/pass2_w8/ab.txt), the 8-wave kernel was faster on every plan
+// measured -- 3520 units of ~9 tiles (MultiSURF 5000 x 5000: pass 2 1.26 ->
+// 1.19 ms) to ~100000 units of ~31 (20000 x 20000: 68.75 -> 66.73 ms), at
+// MultiSURF's, MultiSURF*'s and SURF*'s densities alike -- so neither the
+// segment length nor the density enters; plans smaller than the smallest one
+// measured keep the 4-wave kernels (few rounds of the chip's 512 slots:
+// nothing for the occupancy to hide, and nothing measured).  The pass2_w8
+// test hook forces either; the pass2_generic hook keeps every unit on
+// k_score_sparse3's plain-HIP walk.
+#ifndef FS_W8_MIN_UNITS
+#define FS_W8_MIN_UNITS 3520
+#endif
+constexpr int64_t kW8MinUnits = FS_W8_MIN_UNITS;
+int choose_w8(int64_t units, double tiles_per_seg) {
+  if (test_hooks().pass2_generic == 1) return 0;
+  if (test_hooks().pass2_w8 >= 0) return test_hooks().pass2_w8 != 0 ? 1 : 0;
+  (void)tiles_per_seg;
+  return units >= kW8MinUnits ? 1 : 0;
+}
+
 // Feature-layout part of a plan: everything sized by the kept features
 // (permutation tables, quantised operands, pass-2 partials), rebuilt when
 // the plan is re-targeted to another feature subset (fs_plan_set_features).

@@ -1587,6 +1587,32 @@ s[24:25] stream base, s[26:27] next stream base, s36..s99 two weight sets;
 the temporaries of the prologue and the tile's end are s68..s73 of the
 second set, which holds nothing there.  The compiler keeps s0..s19,
 s28..s35 and s100 up.
+The 8-wave form (FS_SPARSE3_SEG_ASM_W8, k_score_sparse3_w8; W8 below): F = 4
+with b0=14, rowb=1024, sets=(36, 52), setw=16, so that the statement fits the
+64 VGPRs and the SGPRs below s72 that 8 waves per SIMD allow.  Same terms,
+order, waits, fold, counter and priority; what differs:
+  * a step is 2 rows = 16 weights = ONE s_load_dwordx16 into one of two sets
+    of 16 SGPRs, requested at the start of the previous step (a lead of 2
+    rows, not 4); a body is still 8 rows = 4 steps, the weight offset still
+    counts the bodies (256 n after the third step of body n); the stream's
+    last step (rows 62, 63) requests the next tile's first 64 bytes;
+  * LDS rows are 1 KB apart: ds_read_b128 at lds_lane + row * 1024, row <= 63
+    (the read after row 63 goes back to row 0): inside the 64 KB block;
+  * weights: offsets 0 .. 2047 of the same streams in 64-byte loads, highest
+    byte wrow + n_tiles * 65536 - 1 as above;
+  * B rows: one global_load_dwordx4 per column (no + 1024): floats f0 ..
+    f0 + 255 of row y * 128 + wave + 16 c <= n_pad - 1, past PW by less than
+    256 floats (f0 < PW), inside xs's slack as above.
+Registers: v14..v45 B (8 x 4), v46..v53 the ring (2 x 4), v54..v57 sub
+scratch (the fold's f64 temporary, the counter's address, data and return),
+v58 row address, v59..v62 the tile's f32 partials; the four f64 sums are
+"+v" operands, and with them the compiler keeps the tile lists and the two
+lane offsets in v0..v13.  s[20:21] B pointer, s22 tile index, s23 weight
+offset, s[24:25] stream base, s[26:27] next stream base, s36..s51 and
+s52..s67 the two weight sets; the temporaries of the prologue and the tile's
+end are s52..s57 of the second set, which holds nothing there.  The compiler
+keeps s0..s19, s28..s35 (s32..s34 are reserved to it) and s68..s71:
+.sgpr_count 74 of the 80 that still admit 8 waves.
 A/B knobs (profiles/pass2_seg/ab.txt; neither beat the plain form by more
 than the run-to-run spread, so the product uses neither): sub=4, a sub
 scratch of 4 registers with sub / fma in two groups of 4; one_lane=True, the
@@ -1596,13 +1622,20 @@ bank conflict of the plain form.
 """
 
 
-def gen_v3seg(name, F=8, sub=None, one_lane=False):
+# the 8-wave form (k_score_sparse3_w8): see V3SEG_DOC
+W8 = dict(b0=14, rowb=1024, sets=(36, 52), setw=16)
+
+
+def gen_v3seg(name, F=8, sub=None, one_lane=False, b0=30, rowb=2048, sets=(36, 68), setw=32):
     R = F // 4                       # ds_read_b128 per row
     NC = 8                           # columns per wave
     SUB = sub or F                   # sub scratch registers per group
     assert F % SUB == 0 and SUB >= 4
-    SET = [36, 68]
-    B0 = 30
+    SET = list(sets)                 # two weight sets of setw SGPRs
+    RPS = setw // NC                 # rows per step (one set)
+    NL = setw // 16                  # s_load_dwordx16 per step
+    assert setw in (16, 32) and SET[0] % 4 == 0 and SET[1] % 4 == 0 and rowb >= 256 * F // 4 * 4
+    B0 = b0
     RING = B0 + NC * F
     TMP = RING + 2 * F
     VA = TMP + SUB
@@ -1610,8 +1643,9 @@ def gen_v3seg(name, F=8, sub=None, one_lane=False):
     VTOP = ACC + F                   # one past the last fixed VGPR
     assert VTOP <= 127 and B0 % 2 == 0 and TMP % 2 == 0
     T64, ADDR, ONE, RET = TMP, TMP + 2, TMP + 3, TMP + 2
-    ROWB = 2048                      # bytes of a row in the LDS block
+    ROWB = rowb                      # bytes of a row in the LDS block
     BODY = 8                         # rows per unrolled body
+    NS = BODY // RPS                 # steps per body (even: the sets alternate)
     BPTR, KT, OFF, BASE, NBASE = 20, 22, 23, 24, 26
     # temporaries of the prologue and the tile's end, where the second weight
     # set holds nothing (consumed by the last step, not yet requested again)
@@ -1656,20 +1690,23 @@ def gen_v3seg(name, F=8, sub=None, one_lane=False):
             L_ += [f"s_add_u32 s{BPTR}, s{BPTR}, %[bstride]", f"s_addc_u32 s{BPTR + 1}, s{BPTR + 1}, 0"]
         return L_
 
+    def first_loads(o):
+        # a stream's first step
+        return [f"s_load_dwordx16 s[{SET[o] + 16 * q}:{SET[o] + 16 * q + 15}], s[{BASE}:{BASE + 1}], 0x{64 * q:x}"
+                for q in range(NL)]
+
     def step(x, last=False):
         k, o = x % 2, 1 - x % 2
         S = ["s_waitcnt lgkmcnt(0)"]
         if last:  # the next tile's first step, not the bytes past this stream
-            S += [f"s_mov_b64 s[{BASE}:{BASE + 1}], s[{NBASE}:{NBASE + 1}]",
-                  f"s_load_dwordx16 s[{SET[o]}:{SET[o] + 15}], s[{BASE}:{BASE + 1}], 0x0",
-                  f"s_load_dwordx16 s[{SET[o] + 16}:{SET[o] + 31}], s[{BASE}:{BASE + 1}], 0x40"]
+            S += [f"s_mov_b64 s[{BASE}:{BASE + 1}], s[{NBASE}:{NBASE + 1}]"]
+            S += first_loads(o)
         else:
-            S += [f"s_load_dwordx16 s[{SET[o]}:{SET[o] + 15}], s[{BASE}:{BASE + 1}], s{OFF}",
-                  f"s_add_u32 s{OFF}, s{OFF}, 64",
-                  f"s_load_dwordx16 s[{SET[o] + 16}:{SET[o] + 31}], s[{BASE}:{BASE + 1}], s{OFF}",
-                  f"s_add_u32 s{OFF}, s{OFF}, 64"]
-        for j in range(4):
-            i = 4 * x + j
+            for q in range(NL):
+                S += [f"s_load_dwordx16 s[{SET[o] + 16 * q}:{SET[o] + 16 * q + 15}], s[{BASE}:{BASE + 1}], s{OFF}",
+                      f"s_add_u32 s{OFF}, s{OFF}, 64"]
+        for j in range(RPS):
+            i = RPS * x + j
             S += read(i, last)
             if j:  # the step's first row landed with the lgkmcnt(0) above
                 S.append(f"s_waitcnt lgkmcnt({R})")
@@ -1706,8 +1743,7 @@ def gen_v3seg(name, F=8, sub=None, one_lane=False):
 
     lines = [f"s_mov_b32 s{KT}, 0",
              *tile_bases(KT, BASE),
-             f"s_load_dwordx16 s[{SET[0]}:{SET[0] + 15}], s[{BASE}:{BASE + 1}], 0x0",
-             f"s_load_dwordx16 s[{SET[0] + 16}:{SET[0] + 31}], s[{BASE}:{BASE + 1}], 0x40"]
+             *first_loads(0)]
     for c in range(NC):
         lines += bload(c)
     lines += [*[f"v_mov_b32 v{ACC + f}, 0" for f in range(F)],
@@ -1718,14 +1754,15 @@ def gen_v3seg(name, F=8, sub=None, one_lane=False):
     lines.append(f"ds_read_b128 v[{a}:{a + 3}], v{VA}")
     lines += next_bases()
     lines += ["50:",
-              f"s_mov_b32 s{OFF}, 128",
+              f"s_mov_b32 s{OFF}, {4 * setw}",
               "7:"]
-    lines += step(0)
-    # the offset counts the bodies: 256 n after the first step of body n
+    for x in range(NS - 1):
+        lines += step(x)
+    # the offset counts the bodies: 256 n after the last but one step of body n
     lines += [f"s_cmp_eq_u32 s{OFF}, {256 * (64 // BODY)}", "s_cbranch_scc1 9f"]
-    lines += step(1)
+    lines += step(NS - 1)
     lines += ["s_branch 7b", "9:"]
-    lines += step(1, last=True)
+    lines += step(NS - 1, last=True)
     # the tile's end: fold, progress counter, the bases of the tile after next
     for q in range(F):
         lines += [f"v_cvt_f64_f32 v[{T64}:{T64 + 1}], v{ACC + q}",
@@ -1793,5 +1830,6 @@ if __name__ == "__main__":
     text = HEADER
     text += "\n" + gen_v3seg("FS_SPARSE3_SEG_ASM_F8", F=8)
     text += "\n" + gen_v3seg("FS_SPARSE3_SEG_ASM_F4", F=4)
+    text += "\n" + gen_v3seg("FS_SPARSE3_SEG_ASM_W8", F=4, **W8)
     open(path, "w").write(text)
     print("wrote", os.path.normpath(path))

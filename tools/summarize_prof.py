@@ -41,10 +41,11 @@ def main(src, out):
             s["hbm_bytes_per_launch"] = (2.0 * s["fetch_KiB_per_launch"] + s["write_KiB_per_launch"]) * 1024
             s["hbm_GBps"] = s["hbm_bytes_per_launch"] / (s["avg_ms"] * 1e-3) / 1e9
     # pass 2 of the sparse path runs one launch per feature width
-    # (k_score_sparse3<8>, <4> for a tail; k_score_sparse2 in profiles of the
+    # (k_score_sparse3_w8 for the all-continuous blocks of an 8-wave plan,
+    # k_score_sparse3<8>, <4> for a tail; k_score_sparse2 in profiles of the
     # entry-stream walk): bench.py prices them together as "k_score_sparse"
     # (its HIP events span the pass)
-    sparse = ("k_score_sparse2<", "k_score_sparse3<")
+    sparse = ("k_score_sparse2<", "k_score_sparse3<", "k_score_sparse3_w8")
     parts = [s for k, s in stats.items() if k.startswith(sparse)]
     if parts and all("hbm_bytes_per_launch" in s for s in parts):
         stats["k_score_sparse"] = {
