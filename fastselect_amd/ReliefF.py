@@ -176,6 +176,63 @@ class ReliefF(TransformerMixin, BaseEstimator):
         return ResidentRows(self, "ReliefF", plan, n, is_discrete, self.effective_backend_,
                             before_score=warn_small_class)
 
+    def stir_test(self, x: np.ndarray, y: np.ndarray, adjust="fdr_bh"):
+        """Score every feature on the resident plan (the one TuRF re-scores
+        through) and test each score against zero with STIR (Le et al.,
+        Bioinformatics 2019): per feature a pooled two-sample t-test of the
+        diffs over the nearest-miss pairs against those over the nearest-hit
+        pairs, the pairs being (sample, neighbour) over the very
+        ``n_neighbors`` lists the score weighs.  The misses of all other
+        classes are pooled, unweighted (for two classes the published test;
+        for more this project's generalisation), and the reference's self-hit
+        of a class with fewer than ``n_neighbors`` other members is not a
+        pair.  The test treats the pairs as independent, which they are not:
+        the p-values are the method's approximation, not calibrated on noise
+        features.
+
+        adjust : {'fdr_bh', 'bonferroni', None}
+            Multiple-testing adjustment of ``stir_p_values_`` into
+            ``stir_p_adjusted_`` (None: a copy).
+
+        Sets the attributes the resident scorer's ``refit`` sets
+        (``feature_importances_``, ``top_features_``, ...) and ``stir_t_``,
+        ``stir_p_values_`` (P(T_df >= t)), ``stir_p_adjusted_``,
+        ``stir_hit_mean_`` / ``stir_miss_mean_``, ``stir_df_``
+        (|H| + |M| - 2), ``stir_n_hit_pairs_`` and ``stir_n_miss_pairs_``.
+        The resident plan runs on device 0 (``devices_`` says so); ValueError
+        when ``devices`` names more than one device.  ValueError
+        for a single class, and when there are fewer than 2 hit or fewer
+        than 2 miss pairs."""
+        from .MultiSURF import adjust_p_values, stir_p_values
+        if adjust not in ("fdr_bh", "bonferroni", None):
+            raise ValueError(f"adjust must be 'fdr_bh', 'bonferroni' or None; got {adjust!r}")
+        devs = _base.fit_devices(self.devices, _base.effective_backend(self.backend),
+                                 _base.rows_hint(x) or 0)
+        if devs is not None and len(devs) > 1:
+            raise ValueError(f"ReliefF.stir_test runs on one device; got devices={list(devs)!r}")
+        scorer = self._resident_scorer(x, y)
+        if scorer is None:
+            raise ValueError("STIR compares hit pairs with miss pairs: y has a single class, "
+                             "so there are no misses")
+        try:
+            self.devices_ = [0] if self.effective_backend_ == "gpu" else None
+            # a new plan scores every column: nothing to re-target
+            scorer.active = np.arange(scorer.is_discrete.size, dtype=np.int64)
+            scorer.refit(scorer.active, stir=True)
+            sums, n_hit, n_miss = scorer.stir_
+        finally:
+            scorer.close()
+        hit_mean, miss_mean, t, df, sp = _lib.stir_statistics_ex(sums, n_hit, n_miss)
+        self.stir_t_ = t
+        self.stir_df_ = df
+        self.stir_hit_mean_ = hit_mean
+        self.stir_miss_mean_ = miss_mean
+        self.stir_n_hit_pairs_ = int(n_hit)
+        self.stir_n_miss_pairs_ = int(n_miss)
+        self.stir_p_values_ = stir_p_values(t, df, sp)
+        self.stir_p_adjusted_ = adjust_p_values(self.stir_p_values_, adjust)
+        return self
+
     def transform(self, x: np.ndarray) -> np.ndarray:
         """Reduce x to the selected features."""
         check_is_fitted(self)

@@ -59,6 +59,7 @@ EXPORTED = (
     "fs_pair_screen", "fs_pair_screen_last_timing",
     "fs_pair_screen_labels", "fs_pair_labels_last_timing",
     "fs_plan_stir", "fs_stir_statistics", "fs_stir_statistics_ex", "fs_plan_stir_kernel_ms",
+    "fs_plan_score_stir",
 )
 
 
@@ -142,6 +143,7 @@ def _load() -> ctypes.CDLL:
                                         _i32p, _f32p, _int, _u8p, _i64, _i64, _int,
                                         ctypes.c_uint64]
     lib.fs_plan_score.argtypes = [_vp, _vp]
+    lib.fs_plan_score_stir.argtypes = [_vp, _vp, _vp, _vp]
     lib.fs_plan_set_features.argtypes = [_vp, _i64p, _i64]
     lib.fs_plan_pass1.argtypes = [_vp, _vp]
     lib.fs_plan_select.argtypes = [_vp, _vp, _vp]
@@ -240,7 +242,8 @@ def _load() -> ctypes.CDLL:
                  "fs_plan_ref_pass2", "fs_plan_ref_sums", "fs_plan_ref_temp", "fs_plan_info", "fs_plan_set_shard", "fs_multisurf_shards", "fs_plan_calibration", "fs_plan_weighted_pairs",
                  "fs_plan_destroy", "fs_multisurf_score_devices", "fs_relieff_score_devices",
                  "fs_surf_score_devices", "fs_multisurf_score_ex", "fs_relieff_score_ex",
-                 "fs_surf_score_ex", "fs_plan_stir", "fs_stir_statistics", "fs_stir_statistics_ex"):
+                 "fs_surf_score_ex", "fs_plan_stir", "fs_stir_statistics", "fs_stir_statistics_ex",
+                 "fs_plan_score_stir"):
         getattr(lib, name).restype = _int
     return lib
 
@@ -662,7 +665,8 @@ class Plan:
 
     def stir_kernel_ms(self, which: int) -> float:
         """HIP-event time of the last ``stir``'s multiplicity (0) / score (1)
-        kernels over its chunks (``fs_plan_stir_kernel_ms``; -1: unavailable)."""
+        kernels over its chunks, or (2) of the last ``RowsPlan.score_stir``'s
+        k_rf_stir (``fs_plan_stir_kernel_ms``; -1: unavailable)."""
         return float(_lib.fs_plan_stir_kernel_ms(self._h, int(which)))
 
     def ref_mask_words(self) -> int:
@@ -803,6 +807,15 @@ class RowsPlan(Plan):
 
     def score(self, sums_ptr: int) -> None:
         check(_lib.fs_plan_score(self._h, _vp(sums_ptr)))
+
+    def score_stir(self, sums_ptr: int, stir_ptr: int, counts_ptr: int) -> None:
+        """``score`` of a ReliefF plan and, over the same neighbour lists, the
+        STIR sums into stir[4 * n_kept] (S1H, S2H, S1M, S2M per kept feature)
+        and |H|, |M| into counts[2] (``fs_plan_score_stir``); all three in the
+        memory space ``score`` writes to.  ``stir_kernel_ms(2)`` is the STIR
+        kernel's time of the last call on the GPU."""
+        check(_lib.fs_plan_score_stir(self._h, _vp(sums_ptr or None), _vp(stir_ptr or None),
+                                      _vp(counts_ptr or None)))
 
     def ref_temp(self) -> None:
         """Reference order: the score up to the float32 temp rows, whose column

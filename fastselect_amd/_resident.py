@@ -45,7 +45,31 @@ class ResidentRows:
         self.plan.score(out.ctypes.data)
         return out
 
-    def refit(self, active):
+    def score_stir(self):
+        """One ``fs_plan_score_stir`` call on the current feature subset (a
+        ReliefF plan): (score_sums[n_kept], stir_sums (4, n_kept), |H|, |M|),
+        the score sums being ``_sums``'s bits."""
+        n_kept = self.plan.n_kept
+        if self.backend == "gpu":
+            import torch
+            # torch.empty, no fill kernels, and the same ordering as _sums
+            sums = torch.empty(n_kept, dtype=torch.float64, device="cuda")
+            stir = torch.empty(4 * n_kept, dtype=torch.float64, device="cuda")
+            counts = torch.empty(2, dtype=torch.float64, device="cuda")
+            torch.cuda.current_stream().synchronize()
+            # synchronises the plan's stream
+            self.plan.score_stir(sums.data_ptr(), stir.data_ptr(), counts.data_ptr())
+            sums, stir, counts = sums.cpu().numpy(), stir.cpu().numpy(), counts.cpu().numpy()
+        else:
+            sums = np.zeros(n_kept, dtype=np.float64)
+            stir = np.zeros(4 * n_kept, dtype=np.float64)
+            counts = np.zeros(2, dtype=np.float64)
+            self.plan.score_stir(sums.ctypes.data, stir.ctypes.data, counts.ctypes.data)
+        return sums, stir.reshape(4, n_kept), int(counts[0]), int(counts[1])
+
+    def refit(self, active, stir=False):
+        """stir: score through ``score_stir`` and keep its STIR sums and pair
+        counts in ``stir_`` = (sums (4, n_kept), |H|, |M|)."""
         est = self.est
         active = np.asarray(active, dtype=np.int64)
         n_select = est._validate_parameters(self.n, active.size)
@@ -57,7 +81,11 @@ class ResidentRows:
         if self.active is None or not np.array_equal(active, self.active):
             self.plan.set_features(active)
             self.active = active
-        scores = (self._sums(active.size) / self.n).astype(np.float32)
+        if stir:
+            sums, *self.stir_ = self.score_stir()
+        else:
+            sums = self._sums(active.size)
+        scores = (sums / self.n).astype(np.float32)
         est.is_discrete_ = self.is_discrete[active]
         est.feature_importances_ = scores
         est.top_features_ = _base.top_features(scores, n_select)

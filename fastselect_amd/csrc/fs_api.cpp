@@ -828,6 +828,28 @@ int fs_plan_score(fs_plan* pl, double* sums) {
   return cpu::surf_run(pl->P, pl->xp(), pl->n_jobs, pl->r_lo, pl->r_hi, sums);
 }
 
+int fs_plan_score_stir(fs_plan* pl, double* sums, double* stir_sums, double* pair_counts) {
+  if (!pl || !sums || !stir_sums || !pair_counts) {
+    set_error("fs_plan_score_stir: NULL plan or buffer");
+    return FS_EINVAL;
+  }
+  if (pl->P.algo == ALGO_MULTISURF) {
+    set_error("fs_plan_score_stir is for ReliefF plans (MultiSURF: pass1 / select, then "
+              "fs_plan_stir)");
+    return FS_EINVAL;
+  }
+  if (pl->P.algo != ALGO_RELIEFF) {
+    set_error("fs_plan_score_stir: STIR is not built for SURF plans (ReliefF: this call, "
+              "MultiSURF: fs_plan_stir)");
+    return FS_ENOTSUP;
+  }
+  if (pl->g) return gpu::plan_score_stir(pl->g, sums, stir_sums, pair_counts);
+  const int rc = cpu::relieff_run(pl->P, pl->xp(), pl->n_jobs, pl->r_lo, pl->r_hi, sums);
+  if (rc != FS_OK) return rc;
+  return cpu::relieff_stir(pl->P, (const float*)pl->xp(), pl->n_jobs, pl->r_lo, pl->r_hi,
+                           stir_sums, pair_counts);
+}
+
 int fs_plan_set_features(fs_plan* pl, const int64_t* feat_idx, int64_t n_kept) {
   if (!pl) {
     set_error("plan is NULL");

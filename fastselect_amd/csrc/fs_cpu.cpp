@@ -17,6 +17,7 @@
 
 #include "../../include/fastselect_amd.h"
 #include "fs_internal.h"
+#include "fs_stir.h"
 
 namespace fs {
 namespace cpu {
@@ -766,6 +767,26 @@ static bool ref_order_matters(const Prepared& P, const float* X, int64_t i,
     }
   }
   return false;
+}
+
+void relieff_neighbours(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t r_hi,
+                        std::vector<std::vector<int32_t>>& lists) {
+  const int C = P.n_classes;
+  const int64_t rows = std::max<int64_t>(r_hi - r_lo, 0);
+  lists.assign((size_t)rows * C, std::vector<int32_t>());
+  if (rows == 0) return;
+  // the distances and the band of relieff_run
+  std::vector<uint32_t> xq;
+  std::vector<float> xs;
+  std::vector<double> D;
+  quantize(P, x, 0, n_jobs, xq, xs, nullptr);
+  distances(P, xq, 0, 1, n_jobs, D);
+  const double amb = calibrated_band(P, x, 0, n_jobs);
+  parallel_for(rows, n_jobs, [&](int64_t r) {
+    std::vector<std::vector<int32_t>> nbr(C);
+    relieff_select_row(P, (const float*)x, D, r_lo + r, amb, nbr);
+    for (int c = 0; c < C; c++) lists[(size_t)r * C + c].swap(nbr[c]);
+  });
 }
 
 int relieff_run(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t r_hi,

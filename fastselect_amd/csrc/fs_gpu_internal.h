@@ -15,6 +15,7 @@
 //   fs_plan.hip      plan create / layout / shard / score entry points
 //   fs_devices.hip   single-process multi-GPU (the estimators' devices=)
 //   fs_stir.hip      STIR: hit / miss sums of diff and diff^2 over the near pairs
+//   fs_stir_relieff.hip  the same sums over ReliefF's neighbour lists
 //
 // Kernel map and rooflines: DESIGN.md §3.  No float atomics touch scores:
 // every reduction has a fixed order, so two runs of the same input are
@@ -248,6 +249,10 @@ struct Plan {
   // score kernel's start / stop events (plan_stir_kernel_ms), taken on demand
   std::vector<hipEvent_t> ev_stir;
   int stir_chunks = 0;          // chunks the last plan_stir walked
+  // plan_score_stir (fs_stir_relieff.hip): k_rf_stir's start / stop events,
+  // taken on the first call; rf_stir_timed: the last plan_score_stir ran it
+  hipEvent_t ev_rf_stir[2] = {nullptr, nullptr};
+  bool rf_stir_timed = false;
   DevArena mem_plan{device};    // buffers sized by n (live as long as the plan)
   DevArena mem_layout{device};  // buffers sized by the feature layout (PW)
   DevArena mem_shard{device};   // buffers sized by the owned tiles (plan_set_shard)
@@ -383,8 +388,17 @@ int accumulate(double* dst, const double* src, int64_t count, hipStream_t st);
 // plus add[c] when add is given
 int reduce_segments(const double* part, int64_t nrows, int64_t PW, const int64_t* out_pos,
                     double* sums, hipStream_t st, const double* add = nullptr);
-// fs_relieff.hip
-int plan_score_relieff(Plan* g, double* sums_dev);
+// fs_relieff.hip.  kRfRows: focal rows per workgroup of k_rf_update and
+// k_rf_stir (their partials have one row per block of kRfRows).  stir_dev /
+// counts_dev: the optional STIR output (plan_score_stir), summed over the
+// neighbour lists right after the selection.
+constexpr int64_t kRfRows = 64;
+int plan_score_relieff(Plan* g, double* sums_dev, double* stir_dev = nullptr,
+                       double* counts_dev = nullptr);
+// fs_stir_relieff.hip: the four STIR sums and the pair counts of the focal
+// rows' neighbour lists nbr / nfound (relieff_select's, in the call arena)
+int relieff_stir_sums(Plan* g, const int32_t* nbr, const int32_t* nfound, double* stir_dev,
+                      double* counts_dev);
 int relieff_run_one(const Prepared& P, const void* x, int device, int64_t r_lo, int64_t r_hi,
                     double* sums_out, const double* seed = nullptr);
 // fs_plan.hip

@@ -545,6 +545,11 @@ int multisurf_shards(const Prepared& P, int device, int world, int share = 1);
 // ReliefF / SURF plans: float64 score sums of the plan's focal rows
 // (sums_dev[n_kept], device memory), for the plan's current feature subset.
 int plan_score(Plan* g, double* sums_dev);
+// ReliefF plans: plan_score, and in the same call the STIR sums of the plan's
+// neighbour lists (fs_stir.h, "STIR for ReliefF") into stir_dev[4 * n_kept]
+// and |H|, |M| into counts_dev[2] (device memory; fs_stir_relieff.hip).
+// plan_stir_kernel_ms(g, 2): the last call's k_rf_stir time.
+int plan_score_stir(Plan* g, double* sums_dev, double* stir_dev, double* counts_dev);
 int plan_info(const Plan* g, int64_t* tiles, double* pfe, int64_t* refined);
 // Band calibration of the plan's current layout: out[0] = 16-bit operands in
 // use, out[1] / out[2] = rms / max |error| of the sampled pairs' quantised

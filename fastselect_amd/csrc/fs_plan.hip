@@ -14,6 +14,7 @@ void plan_destroy(Plan* g) {
   if (g->x_staged) staged_release(g->x_staged);
   for (auto& e : g->ev) event_put(g->device, e, true);
   for (auto& e : g->ev_stir) event_put(g->device, e, true);
+  for (auto& e : g->ev_rf_stir) event_put(g->device, e, true);
   event_put(g->device, g->ev_fork, false);
   event_put(g->device, g->ev_join, false);
   event_put(g->device, g->ev_star, false);
@@ -967,6 +968,25 @@ int plan_score(Plan* g, double* sums_dev) {
     set_error("fs_plan_score: MultiSURF plans score through pass1 / select / pass2");
     return FS_EINVAL;
   }
+  if (hipStreamSynchronize(g->stream) != hipSuccess && rc == FS_OK) rc = FS_EHIP;
+  g->mem_call.release();
+  return rc;
+}
+
+// plan_score of a ReliefF plan with the STIR output set: the neighbour lists
+// die with the call (mem_call), so their sums are taken inside it.
+int plan_score_stir(Plan* g, double* sums_dev, double* stir_dev, double* counts_dev) {
+  FS_HIP(hipSetDevice(g->device));
+  if (g->P.algo != ALGO_RELIEFF) {
+    set_error("fs_plan_score_stir is for ReliefF plans");
+    return FS_EINVAL;
+  }
+  if (g->P.n_classes > 64) {
+    set_error("GPU ReliefF supports at most 64 classes");
+    return FS_ENOTSUP;
+  }
+  g->rf_stir_timed = false;
+  int rc = plan_score_relieff(g, sums_dev, stir_dev, counts_dev);
   if (hipStreamSynchronize(g->stream) != hipSuccess && rc == FS_OK) rc = FS_EHIP;
   g->mem_call.release();
   return rc;

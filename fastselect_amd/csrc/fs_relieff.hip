@@ -1464,7 +1464,7 @@ __global__ __launch_bounds__(64) void k_rf_ref_ties(
 // blocks of kRfRows); 4 waves per workgroup, wave w handles rows w, w+4, ...
 // of the block.  (64-row blocks: the partials k_reduce then folds are 1/4 of
 // 16-row blocks', and the grid still holds ~10^4 workgroups at n = 20000.)
-constexpr int64_t kRfRows = 64;
+// kRfRows: fs_gpu_internal.h.
 __global__ __launch_bounds__(256) void k_rf_update(const float* __restrict__ xs, int64_t r_lo,
                                                    int64_t r_hi,
                                                    int64_t PW, int64_t PC,
@@ -1759,8 +1759,10 @@ static int relieff_ref_ties(Plan* g, int32_t* nbr, const int32_t* nfound, const 
 }
 
 // ReliefF score sums of the plan's focal rows into sums_dev[n_kept]:
-// pass 1, neighbour selection, then the neighbour-gather update.
-int plan_score_relieff(Plan* g, double* sums_dev) {
+// pass 1, neighbour selection, then the neighbour-gather update.  With
+// stir_dev / counts_dev (plan_score_stir) the STIR sums are taken over the
+// selected lists before anything re-orders them.
+int plan_score_relieff(Plan* g, double* sums_dev, double* stir_dev, double* counts_dev) {
   const Prepared& Q = g->P;
   const int C = Q.n_classes;
   const int64_t k = Q.k_neighbors;
@@ -1786,6 +1788,7 @@ int plan_score_relieff(Plan* g, double* sums_dev) {
     std::fprintf(stderr, "[fs_trace] relieff: %lld exact pairs, %lld tie rows\n",
                  (long long)g->n_refined, (long long)g->n_tie_rows);
   }
+  if (stir_dev != nullptr) FS_TRY(relieff_stir_sums(g, nbr, nfound, stir_dev, counts_dev));
   if (Q.ref_accum) {
     // the reference's order (fs_refacc.hip): neighbour lists in argsort
     // order, float32 temp rows, float32 sequential column sums, continuing

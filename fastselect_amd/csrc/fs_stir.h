@@ -1,4 +1,4 @@
-// fs_stir.h -- STIR: t-statistics for MultiSURF scores.  This header is the
+// fs_stir.h -- STIR: t-statistics for MultiSURF and ReliefF scores.  This header is the
 // specification (there is no reference implementation) and holds the host
 // epilogue both backends' callers share.
 //
@@ -53,6 +53,39 @@
 // far outlier that no near pair includes) gets S2H = S2M = 0, so vH = vM = 0,
 // sp = 0 and t = +inf, -inf or 0, where the exact sums give a finite t.
 // The sums S1 keep their absolute bound there.
+//
+// STIR for ReliefF (fs_plan_score_stir).  The published STIR is defined on
+// ReliefF's k nearest hits and k nearest misses; the MultiSURF form above is
+// the paper's extension.
+//
+// Neighbour sets.  For a focal sample i of the plan's row range [r_lo, r_hi),
+// L_i[c] is the plan's neighbour list of class c: the min(k, members of c
+// other than i) nearest samples of class c by the reference's float32 key
+// (ReliefF.py:145-155), ties at the k-th key resolved in numba's argsort
+// order (ReliefF.py:157-175) -- the very lists the score weighs.  The
+// reference counts the focal sample itself as a zero-diff hit in h_found when
+// its class has fewer than k other members; that self entry is NOT a pair of
+// the test.
+//
+// H is the set of ordered pairs (i, j) with j in L_i[y_i], M the set of
+// ordered pairs (i, j) with j in L_i[c] for any c != y_i.  M is pooled and
+// unweighted: the class-prior weights of the score do not enter.  For two
+// classes this is the published STIR, |H| = |M| = n k when both classes have
+// more than k members; for more classes it is a pooled generalisation, this
+// project's choice.  diff_a, S1H, S2H, S1M, S2M and the epilogue are those
+// above (stir::statistics, fs_stir_statistics unchanged), with
+//
+//   |H| = sum over the focal rows of |L_i[y_i]|
+//   |M| = sum over the focal rows and the classes c != y_i of |L_i[c]|
+//
+// A pair belongs to its focal sample only: row ranges, row panels, devices
+// and ranks partition the pairs and never cut one, so the four sums and both
+// counts add up over disjoint focal-row ranges.  That is why the GPU stage
+// (fs_stir_relieff.hip, k_rf_stir) sums in float64 rather than on the
+// fixed-point grid: regroupings agree to 1e-12, and the terms are |a - b| of
+// the float32 operands xs (each rounded once, ~6e-8 of the feature's range),
+// widened to float64 before they are summed or squared.  The CPU stage
+// (cpu::relieff_stir) sums the reference's float32 diffs widened to float64.
 #pragma once
 
 #include <cmath>
@@ -98,6 +131,18 @@ namespace cpu {
 // focal rows (the same bits for every n_jobs).  x: the plan's float32 X.
 int multisurf_stir(const Prepared& P, const float* x, const CpuState& S, int rank, int world,
                    int n_jobs, int64_t r_lo, int64_t r_hi, double* sums);
+// ReliefF's neighbour lists of the focal rows [r_lo, r_hi) (fs_cpu.cpp):
+// lists[(i - r_lo) * n_classes + c] = L_i[c], selected as relieff_run selects
+// them (relieff_select_row on the same distances and band).
+void relieff_neighbours(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t r_hi,
+                        std::vector<std::vector<int32_t>>& lists);
+// STIR for ReliefF (above): stir_sums[4 n_kept] and pair_counts[2] = |H|, |M|
+// of the focal rows [r_lo, r_hi).  Diffs in the reference's float32
+// arithmetic widened to float64, float64 sums over a partition of the focal
+// rows that depends on the row range alone (the same bits for every n_jobs).
+// x: the plan's float32 X.
+int relieff_stir(const Prepared& P, const float* x, int n_jobs, int64_t r_lo, int64_t r_hi,
+                 double* stir_sums, double* pair_counts);
 }  // namespace cpu
 
 }  // namespace fs

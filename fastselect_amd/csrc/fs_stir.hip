@@ -327,7 +327,17 @@ int plan_stir(Plan* g, double* sums) {
 
 // Summed HIP-event time of the last plan_stir's weights (which == 0) or score
 // (1) kernels over its chunks, in milliseconds; -1 when unavailable.
+// which == 2: k_rf_stir of the last plan_score_stir (fs_stir_relieff.hip).
 double plan_stir_kernel_ms(const Plan* g, int which) {
+  if (which == 2) {
+    float ms = -1.0f;
+    if (!g->rf_stir_timed || hipEventSynchronize(g->ev_rf_stir[1]) != hipSuccess ||
+        hipEventElapsedTime(&ms, g->ev_rf_stir[0], g->ev_rf_stir[1]) != hipSuccess) {
+      (void)hipGetLastError();
+      return -1.0;
+    }
+    return (double)ms;
+  }
   if (g->stir_chunks <= 0 || which < 0 || which > 1) return -1.0;
   double total = 0.0;
   for (int c = 0; c < g->stir_chunks; c++) {

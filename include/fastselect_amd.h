@@ -439,7 +439,8 @@ FS_API int fs_stir_statistics_ex(const double* sums, int64_t n_kept, double n_hi
                                  double* t, double* df, double* pooled_sd);
 /* Summed HIP-event time in milliseconds of the last fs_plan_stir's kernels
  * over its chunks of tiles (GPU only; -1 when unavailable).  which: 0 = the
- * pair-multiplicity kernel, 1 = the score kernel. */
+ * pair-multiplicity kernel, 1 = the score kernel; 2 = k_rf_stir of the last
+ * fs_plan_score_stir on a ReliefF plan (-1 when no such call ran). */
 FS_API double fs_plan_stir_kernel_ms(const fs_plan* plan, int which);
 /* After the three stages of a MultiSURF step, with rowstats[3n], counts[2n]
  * and scores[n_kept] all-reduced (identical on every rank): the 16-bit
@@ -525,6 +526,30 @@ FS_API int fs_plan_create_surf(fs_plan** plan_out, int backend, int device, cons
                                int use_star, const uint8_t* is_discrete, int64_t row_begin,
                                int64_t row_end, int n_jobs, uint64_t stream);
 FS_API int fs_plan_score(fs_plan* plan, double* sums);
+/* STIR for ReliefF (definitions: fastselect_amd/csrc/fs_stir.h, "STIR for
+ * ReliefF"): fs_plan_score on a ReliefF plan, and in the same call the four
+ * STIR sums over the very neighbour lists that score weighs.  H is the set of
+ * ordered pairs (i, j) with j one of focal sample i's nearest hits, M the
+ * same over its nearest misses of every other class, pooled and unweighted
+ * (the class priors of the score do not enter; the published STIR for two
+ * classes, this project's generalisation for more).  The reference's
+ * self-hit (a focal sample counted as its own zero-diff hit when its class
+ * has fewer than k other members) is not a pair.
+ *   sums[n_kept]         what fs_plan_score writes, the same bits;
+ *   stir_sums[4 n_kept]  stir_sums[q * n_kept + k], q = 0..3 for S1H, S2H,
+ *                        S1M, S2M, k in feat_idx order (as fs_plan_stir);
+ *   pair_counts[2]       |H| and |M| as doubles (exact integers).
+ * All three lie in the memory space fs_plan_score uses for sums (device
+ * memory for the GPU backend, host memory for the CPU backend) and cover the
+ * plan's focal rows [row_begin, row_end) and current feature subset; the
+ * sums and counts of disjoint row ranges add up to the whole (a pair belongs
+ * to its focal sample).  An empty row range gives zeros.  fs_stir_statistics
+ * turns the summed sums and counts into t-statistics.  Both accumulation
+ * modes (the neighbour sets are the same); a later fs_plan_score is
+ * unchanged.  SURF plans: FS_ENOTSUP; MultiSURF plans: FS_EINVAL (their STIR
+ * is fs_plan_stir). */
+FS_API int fs_plan_score_stir(fs_plan* plan, double* sums, double* stir_sums,
+                              double* pair_counts);
 /* Number of pair tiles this plan owns, the pair-feature evaluations one full
  * pass1+pass2 performs on this rank (throughput accounting) and the number of
  * ambiguous pairs the last stage 2 recomputed exactly.  NULL outputs are
