@@ -114,6 +114,20 @@ class MultiSURF(TransformerMixin, BaseEstimator):
     over the near-hit / near-miss pairs), ``stir_df_`` (|H| + |M| - 2),
     ``stir_n_hit_pairs_`` and ``stir_n_miss_pairs_`` (|H|, |M|).  MultiSURF*
     (``use_star=True``) has no STIR statistic.
+
+    Calibrated significance (``permutation_test``)
+    ----------------------------------------------
+    ``permutation_test(X, y)`` scores as ``fit`` does and compares every
+    score with its null distribution under permuted labels.  MultiSURF's
+    distances, thresholds and near sets do not read the labels, so they are
+    computed once and all labellings are scored in one pass over the near
+    pairs (``ShardedMultiSURF.score_labels``).  Attributes set beside those
+    of ``fit``: ``p_values_`` (per feature, (1 + #{null >= observed}) /
+    (1 + B)), ``p_values_maxT_`` (Westfall-Young single step: against the
+    largest null score of each permutation over all features, which controls
+    the family-wise error rate), ``null_max_scores_`` (B,), ``null_mean_``
+    and ``null_std_`` (p,), ``null_scores_`` (B, p) with ``keep_null=True``,
+    ``n_permutations_``.
     """
 
     def __init__(
@@ -226,6 +240,66 @@ class MultiSURF(TransformerMixin, BaseEstimator):
         self.stir_p_adjusted_ = adjust_p_values(self.stir_p_values_, adjust)
         return self
 
+    def permutation_test(self, x: np.ndarray, y: np.ndarray, n_permutations=1000,
+                         random_state=None, keep_null=False):
+        """Score every feature as ``fit`` does and give each score a
+        permutation p-value: one resident scoring step, then y itself and
+        ``n_permutations`` uniform permutations of it (drawn from
+        ``np.random.default_rng(random_state)``) scored in one
+        ``score_labels`` call on the step's distances, thresholds and near
+        sets.  Row 0 of that call is y, so the observed scores and the null
+        share one arithmetic.
+
+        Sets the attributes ``fit`` sets (``feature_importances_`` are the
+        resident step's scores) and ``p_values_``, ``p_values_maxT_``,
+        ``null_max_scores_``, ``null_mean_``, ``null_std_``,
+        ``n_permutations_`` and, with ``keep_null=True``, ``null_scores_``
+        (see the class docstring).  The resident job runs on device 0 with the
+        library's default host threads: ``devices`` and ``n_jobs`` are not
+        honoured here as ``fit`` honours them, and ``devices_`` says so.
+        ValueError for ``use_star=True`` (the star's far misses read the
+        labels), for ``accumulation='reference'`` and for
+        ``n_permutations < 1``."""
+        if self.use_star:
+            raise ValueError("the permutation test scores MultiSURF's near pairs on "
+                             "label-independent decisions; MultiSURF* (use_star=True) is not "
+                             "built")
+        _lib.accumulation_code(self.accumulation)
+        if self.accumulation != "fast":
+            raise ValueError("the permutation test runs in accumulation='fast' (the null is not "
+                             "accumulated in reference order)")
+        n_permutations = int(n_permutations)
+        if n_permutations < 1:
+            raise ValueError(f"n_permutations must be >= 1; got {n_permutations}")
+        scorer = _ResidentMultiSURF(self, x, y)
+        try:
+            self.devices_ = [0] if self.effective_backend_ == "gpu" else None
+            scorer.active = np.arange(scorer.is_discrete.size, dtype=np.int64)
+            scorer.refit(scorer.active)
+            y_enc = np.unique(scorer.y, return_inverse=True)[1].astype(np.int32).reshape(-1)
+            rng = np.random.default_rng(random_state)
+            labels = np.empty((n_permutations + 1, y_enc.size), dtype=np.int32)
+            labels[0] = y_enc
+            for b in range(n_permutations):
+                labels[b + 1] = rng.permutation(y_enc)
+            scores = scorer.job.score_labels(labels).cpu().numpy().astype(np.float64)
+        finally:
+            scorer.close()
+        obs, null = scores[0], scores[1:]
+        null_max = null.max(axis=1)
+        self.n_permutations_ = n_permutations
+        self.p_values_ = (1.0 + (null >= obs[None, :]).sum(axis=0)) / (1.0 + n_permutations)
+        self.p_values_maxT_ = ((1.0 + (null_max[:, None] >= obs[None, :]).sum(axis=0))
+                               / (1.0 + n_permutations))
+        self.null_max_scores_ = null_max
+        self.null_mean_ = null.mean(axis=0)
+        self.null_std_ = null.std(axis=0)
+        if keep_null:
+            self.null_scores_ = null
+        elif hasattr(self, "null_scores_"):
+            del self.null_scores_
+        return self
+
     def _resident_scorer(self, x, y):
         """A scorer for TuRF that keeps X resident (on the GPU for the GPU
         backend) and re-scores column subsets through feat_idx, which the
@@ -256,6 +330,7 @@ class _ResidentMultiSURF:
                                  pinned=_base.stage_device(est.backend) is not None)
         est.effective_backend_ = _base.effective_backend(est.backend)
         self.n = x.shape[0]
+        self.y = np.asarray(y)
         self.is_discrete, col_min, col_max = _base.column_preprocess(
             x, est.discrete_limit, est.effective_backend_)
         ranges = (col_max - col_min).astype(np.float32)

@@ -60,6 +60,7 @@ EXPORTED = (
     "fs_pair_screen_labels", "fs_pair_labels_last_timing",
     "fs_plan_stir", "fs_stir_statistics", "fs_stir_statistics_ex", "fs_plan_stir_kernel_ms",
     "fs_plan_score_stir",
+    "fs_plan_score_labels", "fs_multisurf_score_labels", "fs_plan_labels_kernel_ms",
 )
 
 
@@ -154,6 +155,13 @@ def _load() -> ctypes.CDLL:
     lib.fs_stir_statistics_ex.argtypes = list(lib.fs_stir_statistics.argtypes) + [_f64p]
     lib.fs_plan_stir_kernel_ms.argtypes = [_vp, _int]
     lib.fs_plan_stir_kernel_ms.restype = ctypes.c_double
+    lib.fs_plan_score_labels.argtypes = [_vp, _i32p, _i64, _vp]
+    lib.fs_plan_score_labels.restype = _int
+    lib.fs_multisurf_score_labels.argtypes = [_int, _int, _f32p, _i64, _i64, _i32p, _i64, _f32p,
+                                              _i64p, _i64, _u8p, _int, _f32p]
+    lib.fs_multisurf_score_labels.restype = _int
+    lib.fs_plan_labels_kernel_ms.argtypes = [_vp, _int]
+    lib.fs_plan_labels_kernel_ms.restype = ctypes.c_double
     lib.fs_plan_decision_guard.argtypes = [_vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double),
                                            ctypes.POINTER(_int)]
     lib.fs_plan_ref_mask_words.argtypes = [_vp, _i64p]
@@ -545,6 +553,38 @@ def multisurf_score(backend, x, y, recip, feat_idx, use_star, is_discrete, n_job
     return out
 
 
+def _labels_arg(labels, n):
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if lab.ndim == 1:
+        lab = lab.reshape(1, -1)
+    if lab.ndim != 2 or lab.shape[1] != n:
+        raise ValueError(f"labels must have shape (B, {n}); got {lab.shape}")
+    return lab
+
+
+def multisurf_score_labels(backend, x, labels, recip, is_discrete, feat_idx=None, n_jobs=-1,
+                           device=0):
+    """MultiSURF scores of B labellings of the same samples in one call
+    (``fs_multisurf_score_labels``): distances, thresholds and near sets do
+    not depend on the labels, so they are computed once and every labelling
+    only re-weighs the near pairs.  ``labels``: (B, n) integers, compared by
+    equality only.  Returns (B, n_kept) float32; row b is the score vector of
+    ``multisurf_score`` with labelling b as y (CPU backend: bit for bit)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n, p = x.shape
+    lab = _labels_arg(labels, n)
+    rc_ = np.ascontiguousarray(recip, dtype=np.float32)
+    isd = np.ascontiguousarray(is_discrete, dtype=np.uint8)
+    fidx = None if feat_idx is None else np.ascontiguousarray(feat_idx, dtype=np.int64)
+    n_kept = p if fidx is None else fidx.size
+    out = np.zeros((lab.shape[0], n_kept), dtype=np.float32)
+    check(_lib.fs_multisurf_score_labels(_backend_code(backend), int(device), _p(x, _f32p), n, p,
+                                         _p(lab, _i32p), lab.shape[0], _p(rc_, _f32p),
+                                         None if fidx is None else _p(fidx, _i64p), n_kept,
+                                         _p(isd, _u8p), int(n_jobs), _p(out, _f32p)))
+    return out
+
+
 def relieff_score(backend, x, y_enc, recip, is_discrete, k, class_probs, n_jobs=-1, device=0,
                   rows=None, devices=None):
     """Drop-in for ``_relieff_{cpu,gpu}_host_caller`` (ReliefF.py:127-134, 222-236).
@@ -668,6 +708,18 @@ class Plan:
         kernels over its chunks, or (2) of the last ``RowsPlan.score_stir``'s
         k_rf_stir (``fs_plan_stir_kernel_ms``; -1: unavailable)."""
         return float(_lib.fs_plan_stir_kernel_ms(self._h, int(which)))
+
+    def score_labels(self, labels, scores_ptr: int) -> None:
+        """The score sums of the (B, n) int32 host labellings on this plan's
+        decisions into scores[B * n_kept] (``fs_plan_score_labels``), after
+        ``select``; scores in the memory space ``pass2`` writes to."""
+        lab = _labels_arg(labels, self.n)
+        check(_lib.fs_plan_score_labels(self._h, _p(lab, _i32p), lab.shape[0], _vp(scores_ptr)))
+
+    def labels_kernel_ms(self, which: int) -> float:
+        """HIP-event time of the last ``score_labels``' record (0), counts and
+        weights (1) or score (2) kernels (``fs_plan_labels_kernel_ms``; -1: unavailable)."""
+        return float(_lib.fs_plan_labels_kernel_ms(self._h, int(which)))
 
     def ref_mask_words(self) -> int:
         """int64 words of the reference-order decision masks (``fs_plan_ref_mask_words``)."""

@@ -174,6 +174,8 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "pair_lab_ranks") h.pair_lab_ranks = value;
   else if (k == "stir_chunk") h.stir_chunk = value;
   else if (k == "stir_seg_len") h.stir_seg_len = value;
+  else if (k == "labels_chunk") h.labels_chunk = value;
+  else if (k == "labels_seg_len") h.labels_seg_len = value;
   else {
     set_error("fs_test_hook: unknown hook '" + k + "'");
     return FS_EINVAL;
@@ -332,6 +334,37 @@ int fs_multisurf_score_rows(int backend, int device, const float* x, int64_t n, 
   cpu::multisurf_pass1(P, x, 0, 1, n_jobs, st, rs.data());
   cpu::multisurf_select(P, x, 0, 1, rs.data(), n_jobs, st, cnt.data());
   return cpu::multisurf_pass2(P, x, st, cnt.data(), 0, 1, n_jobs, row_begin, row_end, sums_out);
+}
+
+int fs_multisurf_score_labels(int backend, int device, const float* x, int64_t n, int64_t p,
+                              const int32_t* labels, int64_t B, const float* recip,
+                              const int64_t* feat_idx, int64_t n_kept, const uint8_t* is_discrete,
+                              int n_jobs, float* scores_out) {
+  if (!scores_out || !labels || B < 1) {
+    set_error("fs_multisurf_score_labels: need labels, scores_out and B >= 1");
+    return FS_EINVAL;
+  }
+  int rc = check_backend(backend, device);
+  if (rc != FS_OK) return rc;
+  Prepared P;
+  rc = prepare(P, ALGO_MULTISURF, x, 0, n, p, feat_idx, n_kept, recip, is_discrete, n_jobs,
+               backend == FS_BACKEND_GPU);
+  if (rc) return map_prep_rc(rc);
+  if (encode_labels_i32(P, labels)) return FS_EINVAL;  // labelling 0 is the plan's y
+  if ((rc = apply_accumulation(P)) != FS_OK) return rc;
+  if (P.ref_accum) {
+    set_error("fs_multisurf_score_labels: not built for reference-order accumulation");
+    return FS_ENOTSUP;
+  }
+  if (backend == FS_BACKEND_GPU)
+    return gpu::multisurf_labels_run(P, x, device, labels, B, scores_out);
+  cpu::CpuState st;
+  std::vector<double> rs(3 * n), cnt(2 * n), S((size_t)B * P.n_kept);
+  cpu::multisurf_pass1(P, x, 0, 1, n_jobs, st, rs.data());
+  cpu::multisurf_select(P, x, 0, 1, rs.data(), n_jobs, st, cnt.data());
+  if ((rc = cpu::multisurf_score_labels(P, x, st, labels, B, n_jobs, S.data())) != FS_OK) return rc;
+  for (int64_t k = 0; k < B * P.n_kept; k++) scores_out[k] = (float)(S[k] / (double)n);
+  return FS_OK;
 }
 
 // Shared by the one-shot and the row-range entry points: validate, prepare,
@@ -954,6 +987,46 @@ int fs_stir_statistics_ex(const double* sums, int64_t n_kept, double n_hit_pairs
 double fs_plan_stir_kernel_ms(const fs_plan* pl, int which) {
   if (!pl || !pl->g) return -1.0;
   return gpu::plan_stir_kernel_ms(pl->g, which);
+}
+
+int fs_plan_score_labels(fs_plan* pl, const int32_t* labels, int64_t B, double* scores) {
+  if (!pl || B < 0 || (B > 0 && (!labels || !scores))) {
+    set_error("fs_plan_score_labels: NULL plan or buffer, or B < 0");
+    return FS_EINVAL;
+  }
+  if (pl->P.algo != ALGO_MULTISURF) {
+    set_error("fs_plan_score_labels: a MultiSURF plan (ReliefF's neighbours depend on the "
+              "labels; SURF is not built)");
+    return FS_EINVAL;
+  }
+  if (pl->P.use_star) {
+    set_error("fs_plan_score_labels: MultiSURF* is not built (the star split's per-column "
+              "terms read the labels)");
+    return FS_ENOTSUP;
+  }
+  if (pl->P.ref_accum) {
+    set_error("fs_plan_score_labels: not built for reference-order accumulation");
+    return FS_ENOTSUP;
+  }
+  if (pl->world != 1 || pl->r_lo != 0 || pl->r_hi != pl->P.n) {
+    set_error("fs_plan_score_labels: the plan must own every tile and focal row (world 1, no "
+              "fs_plan_set_shard / fs_plan_set_rows): a labelling's counts would need an "
+              "all-reduce of their own");
+    return FS_ENOTSUP;
+  }
+  if (!pl->selected) {
+    set_error("fs_plan_score_labels: no fs_plan_select on the plan's current shard and feature "
+              "set (run pass1 and select after the last re-targeting)");
+    return FS_EINVAL;
+  }
+  if (B == 0) return FS_OK;
+  if (pl->g) return gpu::plan_score_labels(pl->g, labels, B, scores);
+  return cpu::multisurf_score_labels(pl->P, pl->xp(), pl->st, labels, B, pl->n_jobs, scores);
+}
+
+double fs_plan_labels_kernel_ms(const fs_plan* pl, int which) {
+  if (!pl || !pl->g) return -1.0;
+  return gpu::plan_labels_kernel_ms(pl->g, which);
 }
 
 int fs_plan_pass2(fs_plan* pl, const double* counts, double* scores) {

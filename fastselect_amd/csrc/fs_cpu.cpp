@@ -373,7 +373,7 @@ int multisurf_pass1(const Prepared& P, const void* x, int rank, int world, int n
 
 int multisurf_select(const Prepared& P, const void* x, int rank, int world,
                      const double* rowstats, int n_jobs, CpuState& S, double* counts) {
-  const int64_t n = P.n, nb = P.n_pad / kTile;
+  const int64_t n = P.n;
   S.thr.assign(n, 0.0);
   const double nm1 = (double)(n - 1);
   for (int64_t i = 0; i < n; i++) {  // k_thr_ms
@@ -392,7 +392,15 @@ int multisurf_select(const Prepared& P, const void* x, int rank, int world,
       &refined);
   exact_thresholds(P, x, n_jobs, S, refined, dq / std::sqrt((double)std::max<int64_t>(n - 1, 1)) + 2.0,
                    S.thr);
-  parallel_for(n, n_jobs, [&](int64_t i) {  // k_count_ms
+  multisurf_counts(P, rank, world, n_jobs, S, counts);
+  return FS_OK;
+}
+
+// Near hit / miss counts of P's labels on the decisions of S (k_tile_counts).
+void multisurf_counts(const Prepared& P, int rank, int world, int n_jobs, const CpuState& S,
+                      double* counts) {
+  const int64_t n = P.n, nb = P.n_pad / kTile;
+  parallel_for(n, n_jobs, [&](int64_t i) {
     double h = 0.0, m = 0.0;
     for (int64_t j = 0; j < n; j++) {
       if (j == i || !owned(nb, i, j, rank, world)) continue;
@@ -404,7 +412,6 @@ int multisurf_select(const Prepared& P, const void* x, int rank, int world,
     counts[2 * i] = h;
     counts[2 * i + 1] = m;
   });
-  return FS_OK;
 }
 
 // S_c = sum over owned pairs i < j of w_ij * |xs_ic - xs_jc| (or the

@@ -16,6 +16,7 @@
 //   fs_devices.hip   single-process multi-GPU (the estimators' devices=)
 //   fs_stir.hip      STIR: hit / miss sums of diff and diff^2 over the near pairs
 //   fs_stir_relieff.hip  the same sums over ReliefF's neighbour lists
+//   fs_labels.hip    MultiSURF permutation test: many labellings on one plan's decisions
 //
 // Kernel map and rooflines: DESIGN.md §3.  No float atomics touch scores:
 // every reduction has a fixed order, so two runs of the same input are
@@ -140,7 +141,7 @@ __device__ __forceinline__ int64_t d_rd(int tiled, int2 win, int64_t n_pad, int6
 // live and die together sit in one of four arenas, named at each allocation:
 // mem_plan (sized by n: as long as the plan), mem_layout (sized by the feature
 // layout: until the next plan_layout), mem_shard (sized by the owned tiles:
-// until the next plan_set_shard) and mem_call (one plan_score or plan_stir call).  A buffer
+// until the next plan_set_shard) and mem_call (one plan_score, plan_stir or plan_score_labels call).  A buffer
 // that grows on demand is a DevBuf member: reserve() synchronises the streams
 // it is given, frees the old block and allocates the new size.  Kernels take
 // the raw pointer (.p) and capacity (.cap).  plan_destroy synchronises the
@@ -253,6 +254,11 @@ struct Plan {
   // taken on the first call; rf_stir_timed: the last plan_score_stir ran it
   hipEvent_t ev_rf_stir[2] = {nullptr, nullptr};
   bool rf_stir_timed = false;
+  // plan_score_labels (fs_labels.hip): the record kernels' start / stop
+  // events, then per chunk of labellings the counts kernels' and the score
+  // kernel's (plan_labels_kernel_ms), taken on demand
+  std::vector<hipEvent_t> ev_labels;
+  int labels_chunks = -1;       // chunks the last plan_score_labels walked (-1: none)
   DevArena mem_plan{device};    // buffers sized by n (live as long as the plan)
   DevArena mem_layout{device};  // buffers sized by the feature layout (PW)
   DevArena mem_shard{device};   // buffers sized by the owned tiles (plan_set_shard)

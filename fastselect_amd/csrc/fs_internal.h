@@ -159,6 +159,8 @@ struct TestHooks {
   int64_t pair_lab_ranks = 0;  // >= 1: pair ranks per launch of fs_pair_screen_labels (fs_pairscan_labels.hip)
   int64_t stir_chunk = 0;      // >= 1: tiles per chunk of plan_stir's per-pair buffer, up to whole segments (fs_stir.hip)
   int64_t stir_seg_len = 0;    // >= 1: tiles per segment of k_stir_score (plan_stir; small n computes 1)
+  int64_t labels_chunk = 0;    // 1..32: labellings per chunk of plan_score_labels (fs_labels.hip)
+  int64_t labels_seg_len = 0;  // >= 1: tiles per workgroup of k_lab_score (plan_score_labels)
 };
 TestHooks& test_hooks();
 
@@ -382,6 +384,15 @@ int multisurf_select(const Prepared& P, const void* x, int rank, int world,
 // whose chains use the reference's raw diffs; world must then be 1).
 int multisurf_pass2(const Prepared& P, const void* x, const CpuState& S, const double* counts,
                     int rank, int world, int n_jobs, int64_t r_lo, int64_t r_hi, double* scores);
+// MultiSURF permutation test (fs_labels_cpu.cpp): the score sums of B
+// labellings of the plan's samples on the distances, thresholds and decisions
+// of S (world 1, every focal row): per labelling the counts of
+// multisurf_select and multisurf_pass2 on the swapped labels, so row b has
+// the bits a plan created with labelling b as y returns.  scores[b * n_kept + k].
+void multisurf_counts(const Prepared& P, int rank, int world, int n_jobs, const CpuState& S,
+                      double* counts);
+int multisurf_score_labels(const Prepared& P, const void* x, const CpuState& S,
+                           const int32_t* labels, int64_t B, int n_jobs, double* scores);
 // Score sums (not divided by n) of the focal samples [r_lo, r_hi).
 int surf_run(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t r_hi,
              double* scores);
@@ -520,6 +531,17 @@ int plan_pass2(Plan* g, const double* counts_dev, double* scores_dev);
 // plan_stir_kernel_ms: the last call's weights (0) / score (1) kernel time.
 int plan_stir(Plan* g, double* sums_dev);
 double plan_stir_kernel_ms(const Plan* g, int which);
+// MultiSURF permutation test (fs_labels.hip): the score sums of B labellings
+// (labels: host memory, [B][n]) on this plan's distances, thresholds and
+// decisions into scores_dev[B * n_kept], after a plan_select; the plan owns
+// every tile and focal row.  plan_labels_kernel_ms: the last call's record
+// (0), counts + weights (1) and score (2) kernel time, summed over its chunks.
+int plan_score_labels(Plan* g, const int32_t* labels, int64_t B, double* scores_dev);
+double plan_labels_kernel_ms(const Plan* g, int which);
+// One call from host arrays: plan (labelling 0 as y), the step with its
+// decision check, the labellings; scores_out[B * n_kept] divided by n.
+int multisurf_labels_run(const Prepared& P, const void* x, int device, const int32_t* labels,
+                         int64_t B, float* scores_out);
 int64_t ref_mask_words(const Plan* g);
 int plan_ref_masks(Plan* g, uint64_t* masks_dev);
 int plan_ref_pass2(Plan* g, const uint64_t* masks_dev, const double* counts_dev, int64_t row_lo,

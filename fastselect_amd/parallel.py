@@ -460,6 +460,35 @@ class ShardedMultiSURF:
             sums.record_stream(torch.cuda.current_stream(self.tdev))
         return sums.view(4, k), float(c[0]), float(c[1])
 
+    def score_labels(self, labels):
+        """MultiSURF scores of the (B, n) integer labellings ``labels`` on the
+        distances, thresholds and near sets of the last ``step()``
+        (``fs_plan_score_labels``; DESIGN.md §MultiSURF permutation test):
+        a (B, n_kept) float32 tensor, row b what ``step()`` would return with
+        labelling b as y.  Labels are compared by equality only.  The job must
+        hold the whole problem: one rank, one tile shard, no ``rows`` slice
+        (RuntimeError otherwise), MultiSURF without the star, fast
+        accumulation.  The plan's pass-2 state is left alone: the next
+        ``step()`` returns the bits it would have returned."""
+        import torch
+        if not self._stepped:
+            raise ValueError("score_labels() follows a step() on the current feature set: it "
+                             "reads the step's thresholds and decisions")
+        if self.world * self.shards != 1:
+            raise RuntimeError("score_labels(): the job must own every pair tile (one rank, one "
+                               "tile shard)")
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.ndim == 1:
+            lab = lab.reshape(1, -1)
+        with self._on_stream():
+            k = self.plan.n_kept
+            out = torch.zeros(lab.shape[0] * k, dtype=torch.float64, device=self.tdev)
+            self.plan.score_labels(lab, out.data_ptr())
+            s = (out / self.n).float().view(lab.shape[0], k)
+        if self.stream is not None:  # s is consumed on the caller's stream
+            s.record_stream(torch.cuda.current_stream(self.tdev))
+        return s
+
     def info(self):
         return self.plan.info()
 

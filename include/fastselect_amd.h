@@ -442,6 +442,48 @@ FS_API int fs_stir_statistics_ex(const double* sums, int64_t n_kept, double n_hi
  * pair-multiplicity kernel, 1 = the score kernel; 2 = k_rf_stir of the last
  * fs_plan_score_stir on a ReliefF plan (-1 when no such call ran). */
 FS_API double fs_plan_stir_kernel_ms(const fs_plan* plan, int which);
+/* MultiSURF permutation test: many labellings on one plan's decisions.
+ *
+ * Pass 1 and fs_plan_select do not read the labels: the distances, the
+ * thresholds and so the near sets N_i = { j : D_ij < thr_i } hold for every
+ * labelling of the samples.  Labels enter the near hit / miss counts H_i, M_i
+ * and the pair weights only (near hit -1/H_i, near miss +1/M_i), so the score
+ * sums of B labellings are one contraction of the near pairs' diffs with a
+ * B-wide weight vector per pair (fastselect_amd/csrc/fs_labels.hip).
+ *
+ * fs_plan_score_labels: after fs_plan_pass1 + fs_plan_select on a MultiSURF
+ * plan, the score sums (not divided by n) of B labellings of the plan's
+ * samples on its distances, thresholds and decisions.  labels[b * n + i]:
+ * host memory, any int32, compared by equality only (any number of classes).
+ * scores[b * n_kept + k], k in feat_idx order, in the plan's memory space
+ * like fs_plan_pass2's (device memory for the GPU backend).  The call is
+ * synchronous.  The plan must own every tile and the whole row range
+ * (world 1 and all focal rows, else FS_ENOTSUP); MultiSURF* plans and plans in
+ * reference-order accumulation: FS_ENOTSUP; ReliefF / SURF plans: FS_EINVAL;
+ * no fs_plan_select since the last pass 1 or re-targeting: FS_EINVAL.
+ * Honours fs_plan_set_features.  Pass 2's state is untouched: the next
+ * fs_plan_pass2 returns the bits it returned before.  B = 0: FS_OK, nothing
+ * written.  CPU backend: row b is bit for bit what fs_multisurf_score returns
+ * (times n) with labelling b as y.  GPU backend: float32 MFMA partials of at
+ * most 256 pairs folded into float64, fixed summation order (the same call
+ * gives the same bits twice).
+ *
+ * fs_multisurf_score_labels: one call from host arrays -- the plan with
+ * labelling 0 as y, its step (with the 16-bit decision check of
+ * fs_multisurf_score), the labellings; scores_out[b * n_kept + k] divided by
+ * n.  B >= 1.  FS_ENOTSUP when the distance tiles do not fit one device, or
+ * in reference-order accumulation.
+ *
+ * fs_plan_labels_kernel_ms: summed HIP-event time in milliseconds of the last
+ * fs_plan_score_labels' kernels (GPU only; -1 when unavailable).  which: 0 =
+ * the near-pair record kernels (once per call), 1 = the counts and weights
+ * kernels, 2 = the score kernel (both summed over the chunks of labellings). */
+FS_API int fs_plan_score_labels(fs_plan* plan, const int32_t* labels, int64_t B, double* scores);
+FS_API int fs_multisurf_score_labels(int backend, int device, const float* x, int64_t n, int64_t p,
+                                     const int32_t* labels, int64_t B, const float* recip,
+                                     const int64_t* feat_idx, int64_t n_kept,
+                                     const uint8_t* is_discrete, int n_jobs, float* scores_out);
+FS_API double fs_plan_labels_kernel_ms(const fs_plan* plan, int which);
 /* After the three stages of a MultiSURF step, with rowstats[3n], counts[2n]
  * and scores[n_kept] all-reduced (identical on every rank): the 16-bit
  * decision check of fs_multisurf_score (see fs_multisurf_last_guard) for
