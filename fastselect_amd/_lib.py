@@ -61,6 +61,7 @@ EXPORTED = (
     "fs_plan_stir", "fs_stir_statistics", "fs_stir_statistics_ex", "fs_plan_stir_kernel_ms",
     "fs_plan_score_stir",
     "fs_plan_score_labels", "fs_multisurf_score_labels", "fs_plan_labels_kernel_ms",
+    "fs_plan_star_split", "fs_plan_set_star_split", "fs_multisurf_last_star_split",
 )
 
 
@@ -176,6 +177,12 @@ def _load() -> ctypes.CDLL:
     lib.fs_plan_set_shard.argtypes = [_vp, _int, _int]
     lib.fs_multisurf_shards.argtypes = [_int, _i64, _i64, _int, ctypes.POINTER(_int)]
     lib.fs_plan_weighted_pairs.argtypes = [_vp, _i64p]
+    lib.fs_plan_star_split.argtypes = [_vp, ctypes.POINTER(_int)]
+    lib.fs_plan_star_split.restype = _int
+    lib.fs_plan_set_star_split.argtypes = [_vp, _int]
+    lib.fs_plan_set_star_split.restype = _int
+    lib.fs_multisurf_last_star_split.argtypes = [ctypes.POINTER(_int)]
+    lib.fs_multisurf_last_star_split.restype = _int
     lib.fs_plan_kernel_ms.argtypes = [_vp, _int]
     lib.fs_plan_kernel_ms.restype = ctypes.c_double
     lib.fs_plan_destroy.argtypes = [_vp]
@@ -397,6 +404,16 @@ def multisurf_last_guard():
     rerun = _int(0)
     _lib.fs_multisurf_last_guard(ctypes.byref(risk), ctypes.byref(rerun))
     return float(risk.value), bool(rerun.value)
+
+
+def multisurf_last_star_split() -> int:
+    """The star form this thread's last GPU MultiSURF one-shot call ran in
+    (fs_multisurf_last_star_split): 1 = the star split, 0 = dense star
+    weights or no star, -1 = no such call yet.  A ``devices=`` call decides
+    it once for all its devices."""
+    v = _int(-1)
+    check(_lib.fs_multisurf_last_star_split(ctypes.byref(v)))
+    return int(v.value)
 
 
 def device_count() -> int:
@@ -769,6 +786,22 @@ class Plan:
     def set_shard(self, rank: int, world: int) -> None:
         """Re-target to the pair tiles of shard (rank, world) (fs_plan_set_shard)."""
         check(_lib.fs_plan_set_shard(self._h, int(rank), int(world)))
+
+    def star_split(self) -> int:
+        """The plan's star form (``fs_plan_star_split``): 1 = near pairs in
+        pass 2 and the far part from per-column terms, 0 = dense star weights
+        -- and 0 for every plan that never splits (no star, reference-order
+        accumulation, ReliefF, the CPU backend).  The plans that share a
+        MultiSURF* job must all be in one form."""
+        v = _int(0)
+        check(_lib.fs_plan_star_split(self._h, ctypes.byref(v)))
+        return int(v.value)
+
+    def set_star_split(self, split) -> None:
+        """Put the plan into the star form its job agreed on
+        (``fs_plan_set_star_split``), before the first ``pass1``.  ValueError
+        when the split is asked of a plan that cannot take it."""
+        check(_lib.fs_plan_set_star_split(self._h, int(bool(split))))
 
     def calibration(self) -> dict:
         """Refinement-band calibration of the current layout (fs_plan_calibration)."""

@@ -155,6 +155,7 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "ref_q16") h.ref_q16 = value;
   else if (k == "surf_f64") h.surf_f64 = value;
   else if (k == "star_split") h.star_split = value;
+  else if (k == "star_dense_ranks") h.star_dense_ranks = value;
   else if (k == "colsort_star") h.colsort_star = value;
   else if (k == "colsort_bins12") h.colsort_bins12 = value;
   else if (k == "colsort_global") h.colsort_global = value;
@@ -185,6 +186,15 @@ int fs_test_hook(const char* name, int64_t value) {
 
 int fs_multisurf_last_guard(double* risk_out, int* rerun_out) {
   return gpu::multisurf_last_guard(risk_out, rerun_out);
+}
+
+int fs_multisurf_last_star_split(int* split_out) {
+  if (!split_out) {
+    set_error("split_out is NULL");
+    return FS_EINVAL;
+  }
+  *split_out = gpu::multisurf_last_star_split();
+  return FS_OK;
 }
 
 int fs_device_cache_release(void) {
@@ -1237,6 +1247,33 @@ int fs_plan_weighted_pairs(const fs_plan* pl, int64_t* pairs) {
   }
   *pairs = -1;
   if (pl->g) return gpu::plan_weighted_pairs(pl->g, pairs);
+  return FS_OK;
+}
+
+int fs_plan_star_split(const fs_plan* pl, int* split) {
+  if (!pl || !split) {
+    set_error("NULL plan or output");
+    return FS_EINVAL;
+  }
+  *split = pl->g ? gpu::plan_star_split(pl->g) : 0;  // the CPU backend weighs every pair
+  return FS_OK;
+}
+
+int fs_plan_set_star_split(fs_plan* pl, int split) {
+  if (!pl) {
+    set_error("plan is NULL");
+    return FS_EINVAL;
+  }
+  if (pl->g) {
+    const int rc = gpu::plan_set_star_split(pl->g, split);
+    // a new layout: fs_plan_stir / fs_plan_score_labels need a select on it
+    pl->selected = false;
+    return rc;
+  }
+  if (split) {
+    set_error("fs_plan_set_star_split: the CPU backend has no star split");
+    return FS_EINVAL;
+  }
   return FS_OK;
 }
 

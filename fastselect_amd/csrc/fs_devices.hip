@@ -162,6 +162,18 @@ int multisurf_run_devices(const Prepared& P, const void* x, const int* devices, 
   for (int r = 0; r < N; r++)
     V = std::max(V, multisurf_shards(P, devices[r], N, ordinal_share(devices, N, devices[r])));
   const int W = N * V;
+  // One star form for the whole job, decided here, before the threads start:
+  // the minimum of the devices' own choices (the split only where every
+  // device takes it).  A worker choosing inside its plan_create would read
+  // the free memory of a card its peers are allocating on, and a job of split
+  // and dense plans counts some far pairs twice and misses some columns' far
+  // terms.  (rows_run_devices needs none: a SURF* row plan scores its own
+  // focal rows completely in either form.)
+  Prepared PJ = P;
+  PJ.star_form = 1;
+  for (int r = 0; r < N; r++)
+    PJ.star_form = std::min(PJ.star_form, star_split_choice(P, devices[r], r));
+  g_last_star = PJ.star_form;
   const int64_t n = P.n, nk = P.n_kept;
   enable_peers(devices, N);
   DevGroup G(N, devices);
@@ -188,7 +200,7 @@ int multisurf_run_devices(const Prepared& P, const void* x, const int* devices, 
     bool ok = distribute_x(G, r, x, sizeof(float) * (size_t)P.p_in, n, xmem, &xbuf, xs_st,
                            evs[0], rc);
     if (ok && !rc) rc = stage_x_device(devices[r], x, xbuf, 0, n, P.p_in, &staged);
-    if (ok && !rc) rc = plan_create(&g, P, x, 0, devices[r], r, W, 0);
+    if (ok && !rc) rc = plan_create(&g, PJ, x, 0, devices[r], r, W, 0);
     if (staged) unstage_x(staged);
     if (ok && !rc) rc = plan_set_rows(g, r_lo, r_hi);
     const int64_t glen = (int64_t)N * std::max<int64_t>(3 * n, nk);

@@ -415,6 +415,8 @@ int surf_run_one(const Prepared& P, const void* x, int device, int64_t r_lo, int
 // the decision guard's last risk / re-run of this thread (plan_decision_guard)
 extern thread_local double g_last_risk;
 extern thread_local int g_last_rerun;
+// the star form of this thread's last one-shot MultiSURF call (multisurf_last_star_split)
+extern thread_local int g_last_star;
 
 }  // namespace gpu
 }  // namespace fs

@@ -113,6 +113,11 @@ struct Prepared {
   // computes beside k_dist, instead of before it (one-shot calls; a plan
   // switched to 32-bit operands then runs pass 1 again)
   int defer_guard = 0;
+  // MultiSURF* plans of one job must all score the far pairs the same way
+  // (fs_plan.hip choose_star_split): -1 = the plan's own choice, 0 / 1 = the
+  // form its job agreed on (dense star weights / the star split; 1 where the
+  // split does not fit is an error).  multisurf_run_devices sets it.
+  int star_form = -1;
 };
 
 // Accumulation mode of the calling thread's next calls (fs_api.cpp,
@@ -140,6 +145,7 @@ struct TestHooks {
   int64_t ref_q16 = 0;         // 1: reference-order MultiSURF may take 16-bit operands
   int64_t surf_f64 = -1;       // 0 / 1: SURF on integer / float64 distances (surf_band)
   int64_t star_split = -1;     // 0 / 1: MultiSURF* / SURF* dense star weights / near-only + column terms
+  int64_t star_dense_ranks = 0; // bit r: the own choice of a plan created with rank r comes out dense (r < 63)
   int64_t colsort_star = -1;   // 0: MultiSURF* split plans sort twice (binned correction + star sort)
   int64_t colsort_bins12 = 0;  // 1: 4096 bins at every n
   int64_t colsort_global = 0;  // 1: the large-n (device sort) route at every n
@@ -564,6 +570,14 @@ int plan_set_shard(Plan* g, int rank, int world);
 // tile buffers fit the device (1 = no sharding; the shards test hook forces it); with
 // share > 1 that many plans split the device's memory (repeated ordinals).
 int multisurf_shards(const Prepared& P, int device, int world, int share = 1);
+// The star form (1 = split, 0 = dense star weights or no star at all) a plan
+// of P created now on `device` with `rank` would choose by itself, and the
+// form a plan is in; plan_set_star_split re-targets a MultiSURF tile plan to
+// the form its job agreed on (FS_EINVAL for the split where it cannot be
+// taken: no star, reference order, star_split_fits says no).
+int star_split_choice(const Prepared& P, int device, int rank);
+int plan_star_split(const Plan* g);
+int plan_set_star_split(Plan* g, int split);
 // ReliefF / SURF plans: float64 score sums of the plan's focal rows
 // (sums_dev[n_kept], device memory), for the plan's current feature subset.
 int plan_score(Plan* g, double* sums_dev);
@@ -588,6 +602,8 @@ void plan_destroy(Plan* g);
 int multisurf_run(const Prepared& P, const void* x, int device, float* scores_out);
 // The 16-bit decision check of this thread's last multisurf_run (risk, re-run).
 int multisurf_last_guard(double* risk, int* rerun);
+// The star form this thread's last GPU MultiSURF one-shot call ran in (-1: none yet).
+int multisurf_last_star_split();
 // One process, several devices (devices[0..ndev), repeats allowed): MultiSURF
 // tile partition / ReliefF and SURF row partition with host-side rank-order
 // sums in place of the all-reduces.  Score sums of [r_lo, r_hi) (not / n).

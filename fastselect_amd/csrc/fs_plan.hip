@@ -58,9 +58,22 @@ static int choose_q16(const Prepared& P) {
 // feature-major copy of the pass-2 values (xsT, n_pad x PW floats) is taken
 // only while it stays under a quarter of the device's free memory; a plan
 // that large keeps the dense star weights.
-static bool choose_star_split(const Prepared& P, int device) {
-  if (!P.use_star || P.ref_accum || P.algo == ALGO_RELIEFF) return false;
-  if (!star_split_fits(P.n, P.n_classes)) return false;
+// The two forms are the same sum only when every plan of a job is in the
+// same one (a split plan adds its column share's far terms for every pair,
+// a dense one weighs the far pairs of its own tiles), and this choice reads
+// the device's free memory of the moment: callers with several tile plans
+// agree on it (multisurf_run_devices, parallel.py ShardedMultiSURF: the
+// minimum of the plans' own choices) and hand it over as P.star_form or by
+// plan_set_star_split.  The star_dense_ranks test hook makes the own choice
+// of single ranks dense.
+static bool can_star_split(const Prepared& P) {
+  return P.use_star && !P.ref_accum && P.algo != ALGO_RELIEFF &&
+         star_split_fits(P.n, P.n_classes);
+}
+
+static bool choose_star_split(const Prepared& P, int device, int rank) {
+  if (!can_star_split(P)) return false;
+  if (rank >= 0 && rank < 63 && ((test_hooks().star_dense_ranks >> rank) & 1)) return false;
   if (test_hooks().star_split >= 0) return test_hooks().star_split != 0;
   size_t free_b = 0, total_b = 0;
   if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
@@ -189,6 +202,8 @@ int plan_layout(Plan* g) {
   if (g->side2) FS_HIP(hipStreamSynchronize(g->side2));
   g->mem_call.release();  // a plan_stir's buffers on a caller's stream
   g->mem_layout.release();
+  g->xsT = nullptr;  // a plan re-targeted to the dense star form has none (k_quantize tests it)
+  g->tcol = nullptr;
   int rc;
   Q.q16 = g->use_q16;
   if (!Q.ranges_ready) {
@@ -384,6 +399,40 @@ int plan_set_shard(Plan* g, int rank, int world) {
   return shard_segments(g);  // pass-2 segments and this shard's mean-correction columns
 }
 
+int star_split_choice(const Prepared& P, int device, int rank) {
+  return choose_star_split(P, device, rank) ? 1 : 0;
+}
+
+int plan_star_split(const Plan* g) { return g->star_split ? 1 : 0; }
+
+// The plan in the form its job agreed on: the pass-2 form that goes with it
+// (choose_sparse), the split's per-sample buffer and stream, then the shard's
+// buffers and the feature layout in plan_create's order (dense weights or
+// sparse streams; xsT / tcol with the split only).  SURF* row plans are left
+// alone: each scores its own focal rows completely in either form, so a job
+// of them needs no agreement.
+int plan_set_star_split(Plan* g, int split) {
+  const bool want = split != 0;
+  if (want == g->star_split) return FS_OK;
+  if (g->P.algo != ALGO_MULTISURF || g->row_mode) {
+    set_error("the star form of a plan is set for MultiSURF* tile plans only (SURF* row plans "
+              "score their rows completely in either form)");
+    return FS_EINVAL;
+  }
+  if (want && !can_star_split(g->P)) {
+    set_error("the star split cannot be taken by this plan (MultiSURF* in fast accumulation, "
+              "n <= 24576, up to 8 classes)");
+    return FS_EINVAL;
+  }
+  FS_HIP(hipSetDevice(g->device));
+  g->star_split = want;
+  g->sparse = choose_sparse(g, g->P);
+  if (want && !g->alpha) FS_TRY(g->mem_plan.alloc(&g->alpha, g->P.n_pad));
+  if (want && !g->side2 && !(g->side2 = stream_get(g->device))) return FS_EHIP;
+  FS_TRY(plan_set_shard(g, g->rank, g->world));
+  return plan_layout(g);
+}
+
 int plan_create(Plan** out, const Prepared& P, const void* x, int x_is_f64, int device,
                 int rank, int world, uint64_t stream, int64_t r_lo, int64_t r_hi) {
   *out = nullptr;
@@ -484,7 +533,11 @@ int plan_create(Plan** out, const Prepared& P, const void* x, int x_is_f64, int 
     if (Q.ref_accum && (rc = M.alloc(&g->bcnt, (size_t)(Q.n / kExactThrRows + 2))))
       return fail(rc);
   }
-  g->star_split = choose_star_split(Q, device);
+  if (Q.star_form == 1 && !can_star_split(Q)) {
+    set_error("plan: the star split was asked for where it cannot be taken");
+    return fail(FS_EINVAL);
+  }
+  g->star_split = Q.star_form >= 0 ? Q.star_form != 0 : choose_star_split(Q, device, rank);
   g->sparse = choose_sparse(g, Q);
   if (g->star_split && (rc = M.alloc(&g->alpha, Q.n_pad))) return fail(rc);
   if (g->star_split && Q.algo == ALGO_MULTISURF && !(g->side2 = stream_get(device)))
@@ -696,6 +749,8 @@ static int run_multisurf_shards(Plan* g, int shards, int rank, int world, double
 constexpr double kQ16MaxRisk = 5e-6;
 thread_local double g_last_risk = -1.0;
 thread_local int g_last_rerun = 0;
+// the star form the thread's last one-shot MultiSURF call ran in (-1: none yet)
+thread_local int g_last_star = -1;
 
 // The risk above, on the device (q16_decision_risk): the step's exchange
 // vectors stay in HBM and one double comes back (until round 5 three
@@ -793,6 +848,8 @@ int multisurf_last_guard(double* risk, int* rerun) {
   return FS_OK;
 }
 
+int multisurf_last_star_split() { return g_last_star; }
+
 int multisurf_run(const Prepared& P, const void* x, int device, float* scores_out) {
   Plan* g = nullptr;
   g_last_risk = -1.0;
@@ -801,6 +858,7 @@ int multisurf_run(const Prepared& P, const void* x, int device, float* scores_ou
   Prepared Q = P;
   Q.defer_guard = 1;  // decided beside the first pass 1 (row_guard)
   FS_TRY(plan_create(&g, Q, x, 0, device, 0, shards, 0));
+  g_last_star = plan_star_split(g);  // one plan scores every shard: one form
   double *rs = nullptr, *cnt = nullptr, *sc = nullptr;
   int rc, switched = 0;
   double risk = -1.0;
@@ -831,6 +889,7 @@ int multisurf_rows(const Prepared& P, const void* x, int device, int64_t r_lo, i
   Plan* g = nullptr;
   const int shards = multisurf_shards(P, device, 1);
   FS_TRY(plan_create(&g, P, x, 0, device, 0, shards, 0));
+  g_last_star = plan_star_split(g);
   double *rs = nullptr, *cnt = nullptr, *sc = nullptr;
   int rc;
   if ((rc = plan_set_rows(g, r_lo, r_hi)) || (rc = g->mem_plan.alloc(&rs, 3 * P.n)) ||

@@ -211,6 +211,19 @@ class ShardedMultiSURF:
             self.plan = _lib.Plan(backend, x, y, recip, is_discrete, use_star=use_star,
                                   rank=self.rank, world=self.world * self.shards, device=device,
                                   stream=stream)
+            # Every rank must score the far pairs of MultiSURF* in the same
+            # form: a split rank adds its column share's far terms for every
+            # pair, a dense rank weighs the far pairs of its own tiles, so a
+            # mixed job counts some far pairs twice and misses some columns'
+            # terms.  Each plan chose from its own device's free memory; the
+            # split is kept only where every rank took it.  (Row-sharded SURF*
+            # needs none of this: a row plan scores its own focal rows
+            # completely in either form.)
+            if use_star and accumulation != "reference":
+                self.star_split = self._agree_min(self.plan.star_split())
+                self.plan.set_star_split(self.star_split)
+            else:
+                self.star_split = 0
         self.rows = None if rows is None else (int(rows[0]), int(rows[1]))
         self._stepped = False  # a step() has run on the current feature set (stir)
         if rows is not None:  # focal-sample slice: pass 2 sums those samples only
@@ -248,14 +261,18 @@ class ShardedMultiSURF:
             yield
         caller.wait_stream(self.stream)
 
-    def _agree_max(self, v: int) -> int:
+    def _agree_max(self, v: int, op="MAX") -> int:
         """MAX of an integer over the ranks (no collective without a group)."""
         if self.dist is None or self.world == 1:
             return v
         import torch
         t = torch.tensor([v], dtype=torch.int64, device=self.tdev)
-        self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
+        self.dist.all_reduce(t, op=getattr(self.dist.ReduceOp, op))
         return int(t.item())
+
+    def _agree_min(self, v: int) -> int:
+        """MIN of an integer over the ranks."""
+        return self._agree_max(v, op="MIN")
 
     def set_features(self, feat_idx):
         """Score another feature subset of the resident samples from the next
@@ -299,7 +316,11 @@ class ShardedMultiSURF:
         wpr = self._mask_words_per_row()
         R, f0 = self.ref_R, self.ref_f0
         if R == 0:
-            return 0
+            # an empty focal range (rows=(k, k)): no rank has rows, nothing to
+            # exchange; fs_plan_ref_pass2 reads no mask but wants a buffer
+            if self.masks is None:
+                self.masks = torch.zeros(1, dtype=torch.int64, device=self.tdev)
+            return self.masks.data_ptr()
         rows_total = max(self._n_pad(), f0 + self.world * R)
         if self.masks is None:
             # whole-matrix buffer (rows past n_pad stay zero) and the chunk

@@ -119,7 +119,7 @@ FS_API int fs_get_accumulation(void);
  * "colsort_bins12", "colsort_global", "star_split", "colsort_star", "mi_tiles",
  * "list_cap", "cfs_rows_cap", "seg_len", "pass2_generic", "mdr_top_cap",
  * "mdr_ranks", "mdr_blocks", "mdr_labels", "pair_tiles", "pair_cap", "pair_labels",
- * "pair_lab_ranks", "stir_chunk", "stir_seg_len").  FS_EINVAL for an unknown name.
+ * "pair_lab_ranks", "stir_chunk", "stir_seg_len", "star_dense_ranks").  FS_EINVAL for an unknown name.
  * Not thread-safe against concurrent scoring calls.
  */
 FS_API int fs_test_hook(const char* name, int64_t value);
@@ -542,6 +542,30 @@ FS_API int fs_plan_set_rows(fs_plan* plan, int64_t row_begin, int64_t row_end);
  * shards per GPU uses rank + N * v of N * V.  No reference counterpart (the
  * reference streams each focal sample's distance row, MultiSURF.py:174-214). */
 FS_API int fs_plan_set_shard(fs_plan* plan, int rank, int world);
+/* The star form of a plan.  A GPU MultiSURF* plan scores its far pairs in one
+ * of two ways: dense (pass 2 weighs every pair of the tiles it owns) or split
+ * (pass 2 weighs the near pairs, and the far part of EVERY pair comes from
+ * per-column terms, of which a rank adds its share of the columns).  The two
+ * are the same sum only when all plans that share a MultiSURF* job -- the
+ * ranks and shards whose partial vectors are added -- are in one form: a
+ * mixed job counts some far pairs twice and misses some columns' far terms,
+ * silently.  A plan picks its form at creation from its device's free memory
+ * of that moment, so the plans of a job may differ.  Ask each plan with
+ * fs_plan_star_split (1 = split, 0 = dense, and 0 for every plan that never
+ * splits: no star, reference-order accumulation, ReliefF, the CPU backend),
+ * take the minimum over the job, and give it to every plan with
+ * fs_plan_set_star_split before the first fs_plan_pass1 (the GPU plan lays
+ * out its buffers again; X stays resident; a later pass1 / select / pass2
+ * sequence starts over).  FS_EINVAL when the split is asked of a plan that
+ * cannot take it (more than 24576 samples or 8 classes, no star, reference
+ * order, the CPU backend), or either change of a SURF* plan: row plans score
+ * their own focal rows completely in either form and need no agreement.  The
+ * one-shot calls agree by themselves (fs_multisurf_score_devices decides once
+ * for all its devices); fs_multisurf_last_star_split tells the form of this
+ * thread's last GPU fs_multisurf_score[_rows|_devices] call (-1: none yet). */
+FS_API int fs_plan_star_split(const fs_plan* plan, int* split_out);
+FS_API int fs_plan_set_star_split(fs_plan* plan, int split);
+FS_API int fs_multisurf_last_star_split(int* split_out);
 /* Shards per device that keep a MultiSURF job of n samples, p features and
  * `world` ranks within the device's free memory (1 when it fits, or without
  * a GPU; the shards test hook overrides).  The one-shot fs_multisurf_score[_rows]

@@ -89,6 +89,44 @@ def test_plan_lifecycle_cpu():
     np.testing.assert_allclose((sc / 150).astype(np.float32), one, rtol=0, atol=1e-7)
 
 
+def test_star_form_exports_on_the_cpu_backend():
+    """fs_plan_star_split / fs_plan_set_star_split / fs_multisurf_last_star_split:
+    a CPU plan weighs every pair, so it reports the dense form, accepts being
+    told so and refuses the split (an error, not a silent dense plan)."""
+    from fastselect_amd import _lib
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in ("fs_plan_star_split", "fs_plan_set_star_split", "fs_multisurf_last_star_split"):
+        assert hasattr(lib, name), f"{name} not exported"
+        assert name in declared_symbols()
+    rng = np.random.default_rng(2)
+    x = rng.standard_normal((140, 7)).astype(np.float32)
+    y = (x[:, 0] > 0).astype(float)
+    recip = (1 / (x.max(0) - x.min(0))).astype(np.float32)
+    isd = np.zeros(7, bool)
+    for star in (False, True):
+        pl = _lib.Plan("cpu", x, y, recip, isd, use_star=star)
+        try:
+            assert pl.star_split() == 0
+            pl.set_star_split(0)
+            with pytest.raises(ValueError, match="star split"):
+                pl.set_star_split(1)
+            assert pl.star_split() == 0
+            # the refused call left the plan usable
+            rs, cn, sc = np.zeros(420), np.zeros(280), np.zeros(7)
+            pl.pass1(rs.ctypes.data)
+            pl.select(rs.ctypes.data, cn.ctypes.data)
+            pl.pass2(cn.ctypes.data, sc.ctypes.data)
+            one = _lib.multisurf_score("cpu", x, y, recip, None, star, isd)
+            np.testing.assert_allclose((sc / 140).astype(np.float32), one, rtol=0, atol=1e-7)
+        finally:
+            pl.close()
+    raw = _lib.lib()
+    assert raw.fs_plan_star_split(None, None) == _lib.FS_EINVAL
+    assert raw.fs_plan_set_star_split(None, 0) == _lib.FS_EINVAL
+    assert raw.fs_multisurf_last_star_split(None) == _lib.FS_EINVAL
+    assert _lib.multisurf_last_star_split() in (-1, 0, 1)
+
+
 def _np_stats(x, cap):
     nd = np.array([min(np.unique(x[:, f]).size, cap + 1) for f in range(x.shape[1])])
     return x.min(axis=0), x.max(axis=0), nd
