@@ -233,6 +233,79 @@ class ReliefF(TransformerMixin, BaseEstimator):
         self.stir_p_adjusted_ = adjust_p_values(self.stir_p_values_, adjust)
         return self
 
+    def permutation_test(self, x: np.ndarray, y: np.ndarray, n_permutations=1000,
+                         random_state=None, keep_null=False):
+        """Score every feature on the resident plan (as ``stir_test`` does)
+        and give each score a permutation p-value: y itself and
+        ``n_permutations`` uniform permutations of it (drawn from
+        ``np.random.default_rng(random_state)``) are scored in one
+        ``score_labels`` call, which runs the distance pass once and then
+        selects neighbours and updates per labelling.  Row 0 of that call is
+        y, so the observed scores and the null share one arithmetic; a
+        permutation keeps the class sizes, so every labelling has y's priors.
+
+        Sets the attributes the resident scorer's ``refit`` sets
+        (``feature_importances_``, ``top_features_``, ...) and, with ``obs``
+        the scores of row 0 and ``null`` those of the permutations,
+        ``p_values_`` ((1 + #{null_f >= obs_f}) / (1 + n_permutations)),
+        ``p_values_maxT_`` (Westfall-Young: the same against each
+        permutation's largest score), ``null_max_scores_``, ``null_mean_``,
+        ``null_std_``, ``n_permutations_`` and, with ``keep_null=True``,
+        ``null_scores_`` -- defined exactly as ``MultiSURF.permutation_test``
+        defines them.  The resident plan runs on device 0 (``devices_`` says
+        so).  ValueError for a single class, for ``accumulation='reference'``,
+        for ``n_permutations < 1`` and when ``devices`` names more than one
+        device; the small-class UserWarning as ``fit``."""
+        _lib.accumulation_code(self.accumulation)
+        if self.accumulation != "fast":
+            raise ValueError("the permutation test runs in accumulation='fast' (the null is not "
+                             "accumulated in reference order)")
+        n_permutations = int(n_permutations)
+        if n_permutations < 1:
+            raise ValueError(f"n_permutations must be >= 1; got {n_permutations}")
+        devs = _base.fit_devices(self.devices, _base.effective_backend(self.backend),
+                                 _base.rows_hint(x) or 0)
+        if devs is not None and len(devs) > 1:
+            raise ValueError("ReliefF.permutation_test runs on one device; got "
+                             f"devices={list(devs)!r}")
+        y_enc = np.unique(np.asarray(y).reshape(-1), return_inverse=True)[1]
+        y_enc = y_enc.astype(np.int32).reshape(-1)
+        if y_enc.size and int(y_enc.max()) >= 64:
+            raise ValueError("ReliefF.permutation_test scores at most 64 classes")
+        # validates X and y as fit does; its refit below emits fit's small-class
+        # UserWarning (before_score)
+        scorer = self._resident_scorer(x, y)
+        if scorer is None:
+            raise ValueError("a permutation of y is y itself: y has a single class")
+        try:
+            self.devices_ = [0] if self.effective_backend_ == "gpu" else None
+            # a new plan scores every column: nothing to re-target
+            scorer.active = np.arange(scorer.is_discrete.size, dtype=np.int64)
+            scorer.refit(scorer.active)
+            rng = np.random.default_rng(random_state)
+            labels = np.empty((n_permutations + 1, y_enc.size), dtype=np.int32)
+            labels[0] = y_enc
+            for b in range(n_permutations):
+                labels[b + 1] = rng.permutation(y_enc)
+            sums = scorer.score_labels(labels)
+        finally:
+            scorer.close()
+        scores = (sums / scorer.n).astype(np.float32).astype(np.float64)
+        obs, null = scores[0], scores[1:]
+        null_max = null.max(axis=1)
+        self.n_permutations_ = n_permutations
+        self.p_values_ = (1.0 + (null >= obs[None, :]).sum(axis=0)) / (1.0 + n_permutations)
+        self.p_values_maxT_ = ((1.0 + (null_max[:, None] >= obs[None, :]).sum(axis=0))
+                               / (1.0 + n_permutations))
+        self.null_max_scores_ = null_max
+        self.null_mean_ = null.mean(axis=0)
+        self.null_std_ = null.std(axis=0)
+        if keep_null:
+            self.null_scores_ = null
+        elif hasattr(self, "null_scores_"):
+            del self.null_scores_
+        return self
+
     def transform(self, x: np.ndarray) -> np.ndarray:
         """Reduce x to the selected features."""
         check_is_fitted(self)

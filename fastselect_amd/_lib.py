@@ -61,6 +61,8 @@ EXPORTED = (
     "fs_plan_stir", "fs_stir_statistics", "fs_stir_statistics_ex", "fs_plan_stir_kernel_ms",
     "fs_plan_score_stir",
     "fs_plan_score_labels", "fs_multisurf_score_labels", "fs_plan_labels_kernel_ms",
+    "fs_plan_relieff_score_labels", "fs_relieff_score_labels", "fs_plan_relieff_labels_info",
+    "fs_plan_relieff_labels_kernel_ms",
     "fs_plan_star_split", "fs_plan_set_star_split", "fs_multisurf_last_star_split",
 )
 
@@ -163,6 +165,15 @@ def _load() -> ctypes.CDLL:
     lib.fs_multisurf_score_labels.restype = _int
     lib.fs_plan_labels_kernel_ms.argtypes = [_vp, _int]
     lib.fs_plan_labels_kernel_ms.restype = ctypes.c_double
+    lib.fs_plan_relieff_score_labels.argtypes = [_vp, _i32p, _i64, _vp]
+    lib.fs_plan_relieff_score_labels.restype = _int
+    lib.fs_relieff_score_labels.argtypes = [_int, _int, _f32p, _i64, _i64, _i32p, _i64, _f32p,
+                                            _u8p, _i64, _int, _f32p]
+    lib.fs_relieff_score_labels.restype = _int
+    lib.fs_plan_relieff_labels_info.argtypes = [_vp, _i64p]
+    lib.fs_plan_relieff_labels_info.restype = _int
+    lib.fs_plan_relieff_labels_kernel_ms.argtypes = [_vp, _int]
+    lib.fs_plan_relieff_labels_kernel_ms.restype = ctypes.c_double
     lib.fs_plan_decision_guard.argtypes = [_vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double),
                                            ctypes.POINTER(_int)]
     lib.fs_plan_ref_mask_words.argtypes = [_vp, _i64p]
@@ -602,6 +613,26 @@ def multisurf_score_labels(backend, x, labels, recip, is_discrete, feat_idx=None
     return out
 
 
+def relieff_score_labels(backend, x, labels, recip, is_discrete, k, n_jobs=-1, device=0):
+    """ReliefF scores of B labellings of the same samples in one call
+    (``fs_relieff_score_labels``): the distance pass does not read the labels,
+    so it runs once, and every labelling only selects its neighbours and
+    updates.  ``labels``: (B, n) integer class codes in [0, 64); the priors of a
+    labelling are its class shares.  Returns (B, p) float32; row b is the score
+    vector of ``relieff_score`` with labelling b as y (CPU backend: bit for
+    bit)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n, p = x.shape
+    lab = _labels_arg(labels, n)
+    rc_ = np.ascontiguousarray(recip, dtype=np.float32)
+    isd = np.ascontiguousarray(is_discrete, dtype=np.uint8)
+    out = np.zeros((lab.shape[0], p), dtype=np.float32)
+    check(_lib.fs_relieff_score_labels(_backend_code(backend), int(device), _p(x, _f32p), n, p,
+                                       _p(lab, _i32p), lab.shape[0], _p(rc_, _f32p),
+                                       _p(isd, _u8p), int(k), int(n_jobs), _p(out, _f32p)))
+    return out
+
+
 def relieff_score(backend, x, y_enc, recip, is_discrete, k, class_probs, n_jobs=-1, device=0,
                   rows=None, devices=None):
     """Drop-in for ``_relieff_{cpu,gpu}_host_caller`` (ReliefF.py:127-134, 222-236).
@@ -901,6 +932,30 @@ class RowsPlan(Plan):
         kernel's time of the last call on the GPU."""
         check(_lib.fs_plan_score_stir(self._h, _vp(sums_ptr or None), _vp(stir_ptr or None),
                                       _vp(counts_ptr or None)))
+
+    def score_labels(self, labels, scores_ptr: int) -> None:
+        """The ReliefF score sums of the (B, n) int32 host labellings (class
+        codes in [0, 64)) into scores[B * n_kept]
+        (``fs_plan_relieff_score_labels``): pass 1 once, then selection and
+        update per labelling; scores in the memory space ``score`` writes to.
+        The plan's own labels are put back."""
+        lab = _labels_arg(labels, self.n)
+        check(_lib.fs_plan_relieff_score_labels(self._h, _p(lab, _i32p), lab.shape[0],
+                                                _vp(scores_ptr or None)))
+
+    def labels_info(self):
+        """(fast-route labellings, general-route labellings, overflow reruns,
+        candidate depth) of the last ``score_labels``
+        (``fs_plan_relieff_labels_info``)."""
+        v = np.zeros(4, dtype=np.int64)
+        check(_lib.fs_plan_relieff_labels_info(self._h, _p(v, _i64p)))
+        return tuple(int(q) for q in v)
+
+    def labels_kernel_ms(self, which: int) -> float:
+        """HIP-event time of the last ``score_labels``: 0 / 1 / 2 the candidate
+        prefix, walk and score kernels, 3 the general route's selection and
+        update (``fs_plan_relieff_labels_kernel_ms``; -1: unavailable)."""
+        return float(_lib.fs_plan_relieff_labels_kernel_ms(self._h, int(which)))
 
     def ref_temp(self) -> None:
         """Reference order: the score up to the float32 temp rows, whose column

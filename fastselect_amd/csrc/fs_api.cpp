@@ -177,6 +177,9 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "stir_seg_len") h.stir_seg_len = value;
   else if (k == "labels_chunk") h.labels_chunk = value;
   else if (k == "labels_seg_len") h.labels_seg_len = value;
+  else if (k == "rf_labels_route") h.rf_labels_route = value;
+  else if (k == "rf_labels_depth") h.rf_labels_depth = value;
+  else if (k == "rf_labels_depth_cap") h.rf_labels_depth_cap = value;
   else {
     set_error("fs_test_hook: unknown hook '" + k + "'");
     return FS_EINVAL;
@@ -687,6 +690,9 @@ struct fs_plan {
   // a fs_plan_select has run on the current shard, feature set and distances
   // (fs_plan_stir reads its decisions); pass1 and every re-targeting clear it
   bool selected = false;
+  // labellings of the last completed fs_plan_relieff_score_labels on the CPU
+  // backend (-1: none; the GPU plan keeps its own record)
+  int64_t rf_labels_done = -1;
   Prepared P;
   Prepared P0;                  // as created (all columns): discrete tables for re-targeting
   gpu::Plan* g = nullptr;
@@ -1037,6 +1043,84 @@ int fs_plan_score_labels(fs_plan* pl, const int32_t* labels, int64_t B, double* 
 double fs_plan_labels_kernel_ms(const fs_plan* pl, int which) {
   if (!pl || !pl->g) return -1.0;
   return gpu::plan_labels_kernel_ms(pl->g, which);
+}
+
+int fs_plan_relieff_score_labels(fs_plan* pl, const int32_t* labels, int64_t B, double* scores) {
+  if (!pl || B < 0 || (B > 0 && (!labels || !scores))) {
+    set_error("fs_plan_relieff_score_labels: NULL plan or buffer, or B < 0");
+    return FS_EINVAL;
+  }
+  if (pl->P.algo != ALGO_RELIEFF) {
+    set_error("fs_plan_relieff_score_labels: a ReliefF plan (MultiSURF: fs_plan_score_labels; "
+              "SURF is not built)");
+    return FS_EINVAL;
+  }
+  if (pl->P.ref_accum) {
+    set_error("fs_plan_relieff_score_labels: not built for reference-order accumulation");
+    return FS_ENOTSUP;
+  }
+  if (pl->r_lo != 0 || pl->r_hi != pl->P.n) {
+    set_error("fs_plan_relieff_score_labels: the plan must own every focal row [0, n)");
+    return FS_ENOTSUP;
+  }
+  if (B == 0) return FS_OK;
+  pl->rf_labels_done = -1;
+  const int rc = pl->g ? gpu::plan_relieff_score_labels(pl->g, labels, B, scores)
+                       : cpu::relieff_score_labels(pl->P, pl->xp(), labels, B, pl->n_jobs, scores);
+  if (rc == FS_OK) pl->rf_labels_done = B;
+  return rc;
+}
+
+int fs_relieff_score_labels(int backend, int device, const float* x, int64_t n, int64_t p,
+                            const int32_t* labels, int64_t B, const float* recip,
+                            const uint8_t* is_discrete, int64_t k, int n_jobs,
+                            float* scores_out) {
+  if (!scores_out || !labels || B < 1 || k < 0) {
+    set_error("fs_relieff_score_labels: need labels, scores_out, B >= 1 and k >= 0");
+    return FS_EINVAL;
+  }
+  int rc = check_backend(backend, device);
+  if (rc != FS_OK) return rc;
+  Prepared P;
+  rc = prepare(P, ALGO_RELIEFF, x, 0, n, p, nullptr, p, recip, is_discrete, n_jobs,
+               backend == FS_BACKEND_GPU);
+  if (rc) return map_prep_rc(rc);
+  P.k_neighbors = k;
+  if (const int bad = relieff_set_labelling(P, labels)) {  // labelling 0 is the plan's y
+    set_error(bad == 1 ? "fs_relieff_score_labels: labelling 0 holds a class code outside [0, 64)"
+                       : "fs_relieff_score_labels: labelling 0 has fewer than 2 classes");
+    return FS_EINVAL;
+  }
+  if ((rc = apply_accumulation(P)) != FS_OK) return rc;
+  if (P.ref_accum) {
+    set_error("fs_relieff_score_labels: not built for reference-order accumulation");
+    return FS_ENOTSUP;
+  }
+  if (backend == FS_BACKEND_GPU)
+    return gpu::relieff_labels_run(P, x, device, labels, B, scores_out);
+  std::vector<double> S((size_t)B * P.n_kept);
+  if ((rc = cpu::relieff_score_labels(P, x, labels, B, n_jobs, S.data())) != FS_OK) return rc;
+  for (int64_t q = 0; q < B * P.n_kept; q++) scores_out[q] = (float)(S[q] / (double)n);
+  return FS_OK;
+}
+
+int fs_plan_relieff_labels_info(const fs_plan* pl, int64_t out[4]) {
+  if (!pl || !out) {
+    set_error("fs_plan_relieff_labels_info: NULL plan or buffer");
+    return FS_EINVAL;
+  }
+  if (pl->g) return gpu::plan_relieff_labels_info(pl->g, out);
+  if (pl->rf_labels_done < 0) {
+    set_error("fs_plan_relieff_labels_info: no completed fs_plan_relieff_score_labels call");
+    return FS_EINVAL;
+  }
+  out[0] = 0, out[1] = pl->rf_labels_done, out[2] = 0, out[3] = 0;
+  return FS_OK;
+}
+
+double fs_plan_relieff_labels_kernel_ms(const fs_plan* pl, int which) {
+  if (!pl || !pl->g) return -1.0;
+  return gpu::plan_relieff_labels_kernel_ms(pl->g, which);
 }
 
 int fs_plan_pass2(fs_plan* pl, const double* counts, double* scores) {

@@ -796,16 +796,21 @@ void relieff_neighbours(const Prepared& P, const void* x, int n_jobs, int64_t r_
   });
 }
 
+void relieff_shared(const Prepared& P, const void* x, int n_jobs, RelieffShared& S) {
+  std::vector<uint32_t> xq;
+  quantize(P, x, 0, n_jobs, xq, S.xs, nullptr);
+  distances(P, xq, 0, 1, n_jobs, S.D);
+  S.amb = calibrated_band(P, x, 0, n_jobs);
+}
+
 int relieff_run(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t r_hi,
                 double* scores) {
-  std::vector<uint32_t> xq;
-  std::vector<float> xs;
-  std::vector<double> D;
-  quantize(P, x, 0, n_jobs, xq, xs, nullptr);
-  distances(P, xq, 0, 1, n_jobs, D);
-  const int64_t n = P.n, k = P.k_neighbors;
+  RelieffShared SH;
+  relieff_shared(P, x, n_jobs, SH);
+  const std::vector<double>& D = SH.D;
+  const int64_t k = P.k_neighbors;
   const int C = P.n_classes;
-  const double amb = calibrated_band(P, x, 0, n_jobs);
+  const double amb = SH.amb;
   if (P.ref_accum) {
     // the reference's order (ReliefF.py:157-220): each class's neighbours in
     // argsort order (exact float32 keys ascending; equal keys by index, see
@@ -863,6 +868,19 @@ int relieff_run(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int6
     ref_column_sums(temp, rows, nk, scores);
     return FS_OK;
   }
+  return relieff_fast_sums(P, x, SH, n_jobs, r_lo, r_hi, scores);
+}
+
+// Fast accumulation: selection and update of the focal rows [r_lo, r_hi) on
+// the label-independent state S; everything that reads P's labels, class
+// count and priors is in here (relieff_score_labels runs it per labelling).
+int relieff_fast_sums(const Prepared& P, const void* x, const RelieffShared& SH, int n_jobs,
+                      int64_t r_lo, int64_t r_hi, double* scores) {
+  const std::vector<float>& xs = SH.xs;
+  const std::vector<double>& D = SH.D;
+  const int64_t n = P.n, k = P.k_neighbors;
+  const int C = P.n_classes;
+  const double amb = SH.amb;
   // per-row partial sums, folded in row order for determinism
   std::vector<double> part((size_t)n * P.PW, 0.0);
   parallel_for(n, n_jobs, [&](int64_t i) {

@@ -17,6 +17,7 @@
 //   fs_stir.hip      STIR: hit / miss sums of diff and diff^2 over the near pairs
 //   fs_stir_relieff.hip  the same sums over ReliefF's neighbour lists
 //   fs_labels.hip    MultiSURF permutation test: many labellings on one plan's decisions
+//   fs_relieff_labels.hip  ReliefF permutation test: many labellings on one pass 1
 //
 // Kernel map and rooflines: DESIGN.md §3.  No float atomics touch scores:
 // every reduction has a fixed order, so two runs of the same input are
@@ -259,6 +260,15 @@ struct Plan {
   // kernel's (plan_labels_kernel_ms), taken on demand
   std::vector<hipEvent_t> ev_labels;
   int labels_chunks = -1;       // chunks the last plan_score_labels walked (-1: none)
+  // plan_relieff_score_labels (fs_relieff_labels.hip): the last call's route
+  // counts and depth (plan_relieff_labels_info; [0] < 0: no call yet), its
+  // summed kernel times (plan_relieff_labels_kernel_ms) and the two events
+  // that time one labelling's general route and the six of the fast route's
+  // stages (prefix, walk, score), taken on the first call
+  int64_t rf_labels_info[4] = {-1, 0, 0, 0};
+  double rf_labels_ms[4] = {0, 0, 0, 0};
+  hipEvent_t ev_rf_labels[2] = {nullptr, nullptr};
+  hipEvent_t ev_rf_fast[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   DevArena mem_plan{device};    // buffers sized by n (live as long as the plan)
   DevArena mem_layout{device};  // buffers sized by the feature layout (PW)
   DevArena mem_shard{device};   // buffers sized by the owned tiles (plan_set_shard)
@@ -401,6 +411,33 @@ int reduce_segments(const double* part, int64_t nrows, int64_t PW, const int64_t
 constexpr int64_t kRfRows = 64;
 int plan_score_relieff(Plan* g, double* sums_dev, double* stir_dev = nullptr,
                        double* counts_dev = nullptr);
+// Fast accumulation after a selection: k_rf_update over nbr / nfound and the
+// fold into sums_dev (plan_score_relieff's tail); relieff_select_update: the
+// selection first, on resident distances, with the plan's current lab / lab8
+// and g->P's class count (one general-route labelling of
+// plan_relieff_score_labels).
+int relieff_update_fold(Plan* g, const double* dprior, const int32_t* nbr, const int32_t* nfound,
+                        double* part, double* sums_dev);
+int relieff_select_update(Plan* g, const int64_t* dcc, const double* dprior, int32_t* nbr,
+                          int32_t* nfound, double* part, double* sums_dev);
+// Exact float32 keys of whole rows (drows on the device) into keys[nr][n],
+// +inf at the focal sample; and numba's order for the runs of equal keys in
+// the candidate prefixes cand[i][0..lok[i]) (L per row, sorted keys ckeys) of
+// the rows tie_rows (fs_relieff_labels.hip).
+int relieff_exact_rows(Plan* g, const int32_t* drows, int64_t nr, float* keys);
+int relieff_prefix_ties(Plan* g, const std::vector<int32_t>& tie_rows, int64_t L, int32_t* cand,
+                        const int32_t* lok, const float* ckeys);
+// fs_labels.hip, for record lists of other makers (fs_relieff_labels.hip):
+// labT[i * 32 + b] from nb raw labellings on the device (k_lab_transpose);
+// the split of k_lab_score over n_tiles groups of records (labels_seg_len
+// hook honoured); k_lab_score + k_lab_reduce of nb labellings into
+// scores[nb][n_kept] (part: nb * nseg * PW doubles; `scored`: an event
+// recorded between the two).  plan_score_labels launches through them too.
+int lab_transpose(Plan* g, const int32_t* lab_raw, int nb, int32_t* labT);
+void lab_score_split(const Plan* g, int64_t n_tiles, int64_t* seg_len, int64_t* nseg);
+int lab_score_reduce(Plan* g, const int2* rec, const int64_t* goff, const float* W,
+                     int64_t n_tiles, int64_t seg_len, int64_t nseg, int nb, double* part,
+                     double* scores, hipEvent_t scored = nullptr);
 // fs_stir_relieff.hip: the four STIR sums and the pair counts of the focal
 // rows' neighbour lists nbr / nfound (relieff_select's, in the call arena)
 int relieff_stir_sums(Plan* g, const int32_t* nbr, const int32_t* nfound, double* stir_dev,

@@ -167,6 +167,9 @@ struct TestHooks {
   int64_t stir_seg_len = 0;    // >= 1: tiles per segment of k_stir_score (plan_stir; small n computes 1)
   int64_t labels_chunk = 0;    // 1..32: labellings per chunk of plan_score_labels (fs_labels.hip)
   int64_t labels_seg_len = 0;  // >= 1: tiles per workgroup of k_lab_score (plan_score_labels)
+  int64_t rf_labels_route = 0; // 1: every labelling of plan_relieff_score_labels on the general route
+  int64_t rf_labels_depth = 0; // 64 / 128 / 256: the candidate depth L of its fast route
+  int64_t rf_labels_depth_cap = 0;  // >= 1: every row's usable prefix length cut to this (forces overflows)
 };
 TestHooks& test_hooks();
 
@@ -229,6 +232,32 @@ inline uint32_t colsort_eq12(int32_t fx) {
 inline int64_t colsort_eq12_fx(uint32_t q) { return (int64_t)(2 * q + 1) * 2048 - (int64_t(1) << 23); }
 int encode_labels_f64(Prepared& P, const double* y);
 int encode_labels_i32(Prepared& P, const int32_t* y);
+// ReliefF permutation test: put labelling lab[0..n) (class codes in [0, 64))
+// in place of Q's labels, class count (largest code + 1; a code without a
+// member takes no part) and priors ((float)((double)count / (double)n), as
+// the estimator forms them).  cc (optional): the 64 class counts.  Returns 0,
+// 1 for a code outside [0, 64), 2 for fewer than 2 classes present.
+constexpr int kRfLabelCodes = 64;
+inline int relieff_set_labelling(Prepared& Q, const int32_t* lab, int64_t* cc = nullptr) {
+  int64_t cnt[kRfLabelCodes] = {0};
+  int top = -1, present = 0;
+  for (int64_t i = 0; i < Q.n; i++) {
+    const int32_t c = lab[i];
+    if (c < 0 || c >= kRfLabelCodes) return 1;
+    cnt[c]++;
+  }
+  for (int c = 0; c < kRfLabelCodes; c++)
+    if (cnt[c] > 0) top = c, present++;
+  if (present < 2) return 2;
+  Q.labels.assign(lab, lab + Q.n);
+  Q.n_classes = top + 1;
+  Q.class_prior.assign((size_t)top + 1, 0.0);
+  for (int c = 0; c <= top; c++)
+    Q.class_prior[c] = (double)(float)((double)cnt[c] / (double)Q.n);
+  if (cc)
+    for (int c = 0; c < kRfLabelCodes; c++) cc[c] = cnt[c];
+  return 0;
+}
 
 // Upper-triangle tile enumeration: t -> (bi, bj), bi <= bj, row-major over
 // the triangle.  Tile t is owned by rank t % world.
@@ -404,6 +433,23 @@ int surf_run(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t
              double* scores);
 int relieff_run(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t r_hi,
                 double* scores);
+// What relieff_run computes before it reads a label: the pass-2 operands, the
+// quantised distances and the calibrated refinement band.
+struct RelieffShared {
+  std::vector<float> xs;
+  std::vector<double> D;
+  double amb = 0.0;
+};
+void relieff_shared(const Prepared& P, const void* x, int n_jobs, RelieffShared& S);
+// relieff_run's fast-accumulation selection and update on that state.
+int relieff_fast_sums(const Prepared& P, const void* x, const RelieffShared& S, int n_jobs,
+                      int64_t r_lo, int64_t r_hi, double* scores);
+// ReliefF permutation test (fs_relieff_labels_cpu.cpp): the score sums of B
+// labellings of P's samples (fast accumulation, every focal row); row b has
+// the bits relieff_run returns for a problem with labelling b as y.
+// scores[b * n_kept + k].
+int relieff_score_labels(const Prepared& P, const void* x, const int32_t* labels, int64_t B,
+                         int n_jobs, double* scores);
 int column_stats(const void* x, int x_is_f64, int64_t n, int64_t p, int64_t cap, int n_jobs,
                  void* colmin, void* colmax, int64_t* ndistinct);
 }  // namespace cpu
@@ -548,6 +594,25 @@ double plan_labels_kernel_ms(const Plan* g, int which);
 // decision check, the labellings; scores_out[B * n_kept] divided by n.
 int multisurf_labels_run(const Prepared& P, const void* x, int device, const int32_t* labels,
                          int64_t B, float* scores_out);
+// ReliefF permutation test (fs_relieff_labels.hip): the score sums of B
+// labellings (labels: host memory, [B][n], codes in [0, 64)) of a ReliefF plan
+// that owns every focal row, into scores_dev[B * n_kept].  Pass 1 runs once
+// per call.  General route: per labelling the plan's selection and update on
+// the resident keys with the labelling in place of the plan's labels, class
+// counts and priors, which are put back before the call returns.  Fast route:
+// one ordered candidate prefix per row for the whole call, per chunk of 32
+// labellings a walk that weighs the candidates, and fs_labels.hip's score
+// kernel.  plan_relieff_labels_info: labellings on the fast route, on the
+// general route by the rule, rerun after an overflow, the candidate depth.
+// plan_relieff_labels_kernel_ms: the last call's candidate prefix (0), walk
+// and weights (1), score kernel (2) and general-route kernels (3).
+int plan_relieff_score_labels(Plan* g, const int32_t* labels, int64_t B, double* scores_dev);
+int plan_relieff_labels_info(const Plan* g, int64_t* out4);
+double plan_relieff_labels_kernel_ms(const Plan* g, int which);
+// One call from host arrays: plan (labelling 0 as y), then the labellings;
+// scores_out[B * n_kept] divided by n.
+int relieff_labels_run(const Prepared& P, const void* x, int device, const int32_t* labels,
+                       int64_t B, float* scores_out);
 int64_t ref_mask_words(const Plan* g);
 int plan_ref_masks(Plan* g, uint64_t* masks_dev);
 int plan_ref_pass2(Plan* g, const uint64_t* masks_dev, const double* counts_dev, int64_t row_lo,

@@ -397,6 +397,34 @@ __global__ __launch_bounds__(256) void k_lab_reduce(const double* __restrict__ p
   scores[b * n_kept + o] = s;
 }
 
+int lab_transpose(Plan* g, const int32_t* lab_raw, int nb, int32_t* labT) {
+  const int64_t n = g->P.n;
+  k_lab_transpose<<<(unsigned)((n * kLabB + 255) / 256), 256, 0, g->stream>>>(lab_raw, n, nb, labT);
+  return launch_check("k_lab_transpose");
+}
+
+void lab_score_split(const Plan* g, int64_t n_tiles, int64_t* seg_len, int64_t* nseg) {
+  const int64_t nfb = (g->P.PW + kLabFeat * kLabWaves - 1) / (kLabFeat * kLabWaves);
+  *seg_len = std::max<int64_t>(1, (n_tiles * nfb + kLabWorkgroups - 1) / kLabWorkgroups);
+  if (test_hooks().labels_seg_len >= 1) *seg_len = test_hooks().labels_seg_len;
+  *nseg = (n_tiles + *seg_len - 1) / *seg_len;
+}
+
+int lab_score_reduce(Plan* g, const int2* rec, const int64_t* goff, const float* W,
+                     int64_t n_tiles, int64_t seg_len, int64_t nseg, int nb, double* part,
+                     double* scores, hipEvent_t scored) {
+  const Prepared& Q = g->P;
+  const int64_t nfb = (Q.PW + kLabFeat * kLabWaves - 1) / (kLabFeat * kLabWaves);
+  const int64_t seg_per_xcd = (nseg + kXcds - 1) / kXcds;
+  k_lab_score<<<(unsigned)(kXcds * seg_per_xcd * nfb), 64 * kLabWaves, 0, g->stream>>>(
+      g->xs, Q.PW, Q.PC, rec, goff, W, n_tiles, seg_len, nseg, nfb, nb, part);
+  FS_TRY(launch_check("k_lab_score"));
+  if (scored) FS_HIP(hipEventRecord(scored, g->stream));
+  k_lab_reduce<<<dim3((unsigned)((Q.PW + 255) / 256), (unsigned)nb), 256, 0, g->stream>>>(
+      part, nseg, Q.PW, g->out_pos, Q.n_kept, scores);
+  return launch_check("k_lab_reduce");
+}
+
 static int labels_events(Plan* g, size_t count) {
   while (g->ev_labels.size() < count) {
     hipEvent_t e = event_get(g->device, true);
@@ -451,11 +479,8 @@ int plan_score_labels(Plan* g, const int32_t* labels, int64_t B, double* scores)
   FS_TRY(launch_check("k_lab_fill"));
   FS_HIP(hipEventRecord(g->ev_labels[1], st));
   // ---- the split of the score kernel: whole tiles per workgroup
-  const int64_t nfb = (Q.PW + kLabFeat * kLabWaves - 1) / (kLabFeat * kLabWaves);
-  int64_t seg_len = std::max<int64_t>(1, (g->n_tiles * nfb + kLabWorkgroups - 1) / kLabWorkgroups);
-  if (test_hooks().labels_seg_len >= 1) seg_len = test_hooks().labels_seg_len;
-  const int64_t nseg = (g->n_tiles + seg_len - 1) / seg_len;
-  const int64_t seg_per_xcd = (nseg + kXcds - 1) / kXcds;
+  int64_t seg_len = 1, nseg = 1;
+  lab_score_split(g, g->n_tiles, &seg_len, &nseg);
   // ---- a chunk's buffers: sized by n, PW and the split, not by B
   int32_t *lab_raw = nullptr, *labT = nullptr;
   double2* U = nullptr;
@@ -490,13 +515,8 @@ int plan_score_labels(Plan* g, const int32_t* labels, int64_t B, double* scores)
     }
     FS_HIP(hipEventRecord(ev[1], st));
     FS_HIP(hipEventRecord(ev[2], st));
-    k_lab_score<<<(unsigned)(kXcds * seg_per_xcd * nfb), 64 * kLabWaves, 0, st>>>(
-        g->xs, Q.PW, Q.PC, rec, goff, W, g->n_tiles, seg_len, nseg, nfb, nb, part);
-    FS_TRY(launch_check("k_lab_score"));
-    FS_HIP(hipEventRecord(ev[3], st));
-    k_lab_reduce<<<dim3((unsigned)((Q.PW + 255) / 256), (unsigned)nb), 256, 0, st>>>(
-        part, nseg, Q.PW, g->out_pos, Q.n_kept, scores + b0 * Q.n_kept);
-    FS_TRY(launch_check("k_lab_reduce"));
+    FS_TRY(lab_score_reduce(g, rec, goff, W, g->n_tiles, seg_len, nseg, nb, part,
+                            scores + b0 * Q.n_kept, ev[3]));
     g->labels_chunks = (int)(c + 1);
   }
   // the labels are host memory: the call ends when the device has finished

@@ -16,6 +16,8 @@ void plan_destroy(Plan* g) {
   for (auto& e : g->ev_stir) event_put(g->device, e, true);
   for (auto& e : g->ev_rf_stir) event_put(g->device, e, true);
   for (auto& e : g->ev_labels) event_put(g->device, e, true);
+  for (auto& e : g->ev_rf_labels) event_put(g->device, e, true);
+  for (auto& e : g->ev_rf_fast) event_put(g->device, e, true);
   event_put(g->device, g->ev_fork, false);
   event_put(g->device, g->ev_join, false);
   event_put(g->device, g->ev_star, false);

@@ -1815,12 +1815,91 @@ int plan_score_relieff(Plan* g, double* sums_dev, double* stir_dev, double* coun
     return refacc::column_sums(temp, rows, g->Kp, Q.n_kept, g->ref_seeded ? sums_dev : nullptr,
                                 sums_dev, g->stream);
   }
+  return relieff_update_fold(g, dprior, nbr, nfound, part, sums_dev);
+}
+
+// Fast accumulation after the selection: the update of the plan's focal rows
+// over the lists nbr / nfound and the fold of the row blocks' partials into
+// sums_dev, with the plan's current lab and the class count of g->P.
+int relieff_update_fold(Plan* g, const double* dprior, const int32_t* nbr, const int32_t* nfound,
+                        double* part, double* sums_dev) {
+  const Prepared& Q = g->P;
+  const int64_t nrb = std::max<int64_t>(1, (g->r_hi - g->r_lo + kRfRows - 1) / kRfRows);
   k_rf_update<<<dim3((unsigned)(Q.PW / 64), (unsigned)nrb), 256, 0, g->stream>>>(
-      g->xs, g->r_lo, g->r_hi, Q.PW, Q.PC, g->lab, dprior, C, k, nbr, nfound, part);
+      g->xs, g->r_lo, g->r_hi, Q.PW, Q.PC, g->lab, dprior, Q.n_classes, Q.k_neighbors, nbr,
+      nfound, part);
   FS_TRY(launch_check("k_rf_update"));
   FS_HIP(hipEventRecord(g->ev[3], g->stream));
   FS_HIP(hipMemsetAsync(sums_dev, 0, sizeof(double) * Q.n_kept, g->stream));
   return reduce_segments(part, nrb, Q.PW, g->out_pos, sums_dev, g->stream);
+}
+
+// One labelling of plan_relieff_score_labels on distances that are resident
+// already: plan_score_relieff's selection, update and fold.
+int relieff_select_update(Plan* g, const int64_t* dcc, const double* dprior, int32_t* nbr,
+                          int32_t* nfound, double* part, double* sums_dev) {
+  FS_TRY(relieff_select(g, dcc, nbr, nfound));
+  return relieff_update_fold(g, dprior, nbr, nfound, part, sums_dev);
+}
+
+// The reference's exact float32 keys of the rows drows[0..nr) (device) into
+// keys[nr][n], +inf at the focal sample (k_rf_exact_rows: k_rf_select's
+// exact-key arithmetic; an all-discrete layout copies the plan's keys).
+int relieff_exact_rows(Plan* g, const int32_t* drows, int64_t nr, float* keys) {
+  const Prepared& Q = g->P;
+  if (nr <= 0) return FS_OK;
+  k_rf_exact_rows<float><<<dim3((unsigned)nr, (unsigned)((Q.n + 3) / 4)), 256, 0, g->stream>>>(
+      (const float*)g->x, Q.n, Q.p_in, Q.pc, Q.PC, Q.pd, g->src_col, g->scl, drows, g->D, g->Dk,
+      Q.n_pad, 1.0 / Q.SC, keys);
+  return launch_check("k_rf_exact_rows");
+}
+
+// Candidate prefixes (fs_relieff_labels.hip): cand[i][0..lok[i]) of the rows
+// tie_rows, sorted by exact key and then index (ckeys: the sorted keys, L per
+// row), get their runs of equal keys in numba's quicksort order: k_rf_ref_ties
+// with the prefix as the one list of the row (C = 1, k = L), over the row's
+// exact keys.
+int relieff_prefix_ties(Plan* g, const std::vector<int32_t>& tie_rows, int64_t L, int32_t* cand,
+                        const int32_t* lok, const float* ckeys) {
+  const int64_t n = g->P.n;
+  if (tie_rows.empty()) return FS_OK;
+  const int64_t row_bytes = 8 * n + 4 * L;
+  const int64_t batch = std::max<int64_t>(
+      1, std::min<int64_t>((int64_t)tie_rows.size(), (int64_t)(512ll << 20) / row_bytes));
+  int32_t *drows = nullptr, *R = nullptr, *ord = nullptr;
+  float* keys = nullptr;
+  int* status = nullptr;
+  DevArena& M = g->mem_call;
+  FS_TRY(M.alloc(&drows, (size_t)batch));
+  FS_TRY(M.alloc(&R, (size_t)(batch * n)));
+  FS_TRY(M.alloc(&keys, (size_t)(batch * n)));
+  FS_TRY(M.alloc(&ord, (size_t)(batch * L)));
+  FS_TRY(M.alloc(&status, 1));
+  FS_HIP(hipMemsetAsync(status, 0, sizeof(int), g->stream));
+  const bool in_lds = 8 * n + 2304 <= 160 * 1024;
+  if (in_lds)
+    FS_HIP(hipFuncSetAttribute((const void*)k_rf_ref_ties<true>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)(8 * n)));
+  for (int64_t r0 = 0; r0 < (int64_t)tie_rows.size(); r0 += batch) {
+    const int64_t nr = std::min<int64_t>(batch, (int64_t)tie_rows.size() - r0);
+    FS_TRY(h2d(g, drows, tie_rows.data() + r0, (size_t)nr));
+    FS_TRY(relieff_exact_rows(g, drows, nr, keys));
+    if (in_lds)
+      k_rf_ref_ties<true><<<(unsigned)nr, 64, (size_t)(8 * n), g->stream>>>(
+          drows, n, keys, 1, L, 0, cand, lok, ckeys, R, ord, status);
+    else
+      k_rf_ref_ties<false><<<(unsigned)nr, 64, 0, g->stream>>>(drows, n, keys, 1, L, 0, cand, lok,
+                                                              ckeys, R, ord, status);
+    FS_TRY(launch_check("k_rf_ref_ties"));
+  }
+  int hstatus = 0;
+  FS_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+  FS_HIP(hipStreamSynchronize(g->stream));
+  if (hstatus != 0) {
+    set_error("ReliefF candidate prefix: quicksort stack overflow");
+    return FS_EHIP;
+  }
+  return FS_OK;
 }
 
 int relieff_run_one(const Prepared& P, const void* x, int device, int64_t r_lo, int64_t r_hi,

@@ -484,6 +484,73 @@ FS_API int fs_multisurf_score_labels(int backend, int device, const float* x, in
                                      const int64_t* feat_idx, int64_t n_kept,
                                      const uint8_t* is_discrete, int n_jobs, float* scores_out);
 FS_API double fs_plan_labels_kernel_ms(const fs_plan* plan, int which);
+/* ReliefF permutation test: many labellings on one distance pass.
+ *
+ * ReliefF's neighbour sets read the labels (the k nearest of every class), so
+ * fs_plan_score_labels stays FS_EINVAL for ReliefF plans.  Two things do not
+ * read them: the distance pass, and the order in which the reference walks a
+ * row (one argsort of its float32 keys): for any labelling the k nearest of a
+ * class are the first k of that class on that walk.  These calls run pass 1
+ * once and then score the labellings on one of two routes
+ * (fastselect_amd/csrc/fs_relieff_labels.hip): the general route, the plan's
+ * own selection and update per labelling on the resident keys; and, on the
+ * GPU, the fast route, which lists every row's first L candidates of that walk
+ * once per call (exact keys, ties in the reference's quicksort order), gives
+ * each candidate a weight per labelling and scores 32 labellings at a time
+ * with the MFMA kernel of fs_plan_score_labels.  A labelling takes the general
+ * route when a class present in it has at most k members, when it has more
+ * than 8 classes, when min(ceil(3 k / its smallest class share), n - 1) exceeds
+ * 256, when a class ran short of k inside some row's prefix (caught and
+ * rerun), and when fewer than 8 labellings of the call qualify for the fast
+ * route or its once-per-call prefix is estimated to cost more than two thirds
+ * of the general route for them.  L is the smallest of 64, 128, 256 that covers the largest need.
+ *
+ * fs_plan_relieff_score_labels: the ReliefF score sums (not divided by n) of
+ * B labellings of the plan's samples.  labels[b * n + i]: host memory, int32
+ * class codes in [0, 64).  The priors of labelling b are
+ * (float)((double)count_c / (double)n); a code with no member in a labelling
+ * takes no part; neighbours are chosen exactly as fs_relieff_score chooses
+ * them (float32 keys, ties in the reference's quicksort order), the self-hit
+ * of a class with fewer than k other members included.  scores[b * n_kept +
+ * k], k in feat_idx order, in the plan's memory space like fs_plan_score's
+ * sums.  The call is synchronous and runs pass 1 for the plan's current
+ * feature subset itself (it honours fs_plan_set_features and needs no earlier
+ * fs_plan_score).  B = 0: FS_OK, nothing written.  FS_EINVAL: a MultiSURF or
+ * SURF plan, a code outside [0, 64), a labelling with fewer than 2 classes
+ * present (checked for every labelling before any is scored).  FS_ENOTSUP: a
+ * plan that does not own the whole focal range [0, n), or one in
+ * reference-order accumulation.  The plan's own labels, priors and neighbour
+ * state are restored: a later fs_plan_score returns the bits it returned
+ * before.  A general-route row b (every row of the CPU backend) is bit for
+ * bit what fs_plan_score of a plan of the same backend created with labelling
+ * b returns; a fast-route row has the same neighbours, float32 weights and
+ * float32 MFMA partials of at most 256 records folded into float64 (within
+ * 1e-5 of the two non-cancelling sums a score is made of).  No float atomics:
+ * the same call gives the same bits twice.
+ *
+ * fs_relieff_score_labels: one call from host arrays (every column scored);
+ * scores_out[b * p + f] divided by n.  B >= 1.  Fast accumulation only
+ * (FS_ENOTSUP in reference order).
+ *
+ * fs_plan_relieff_labels_info: out[0..4) of the last completed call: the
+ * labellings scored on the fast route (0 on the CPU backend), the labellings
+ * sent to the general route by the rule, the fast-route labellings rerun after
+ * an overflow, the candidate depth L (0: no fast route).  FS_EINVAL before the
+ * first call.
+ *
+ * fs_plan_relieff_labels_kernel_ms: summed HIP-event time in milliseconds of
+ * the last call (GPU only; -1 when unavailable).  which: 0 = the candidate
+ * prefix (once per call), 1 = walk and weights, 2 = the score kernel (both
+ * summed over the chunks of labellings), 3 = the general route's selection and
+ * update, summed over its labellings. */
+FS_API int fs_plan_relieff_score_labels(fs_plan* plan, const int32_t* labels, int64_t B,
+                                        double* scores);
+FS_API int fs_relieff_score_labels(int backend, int device, const float* x, int64_t n, int64_t p,
+                                   const int32_t* labels, int64_t B, const float* recip,
+                                   const uint8_t* is_discrete, int64_t k, int n_jobs,
+                                   float* scores_out);
+FS_API int fs_plan_relieff_labels_info(const fs_plan* plan, int64_t out[4]);
+FS_API double fs_plan_relieff_labels_kernel_ms(const fs_plan* plan, int which);
 /* After the three stages of a MultiSURF step, with rowstats[3n], counts[2n]
  * and scores[n_kept] all-reduced (identical on every rank): the 16-bit
  * decision check of fs_multisurf_score (see fs_multisurf_last_guard) for
