@@ -16,6 +16,8 @@ the class against correlation within the subset, and ``JMI`` (JMI / CMIM) select
 by joint relevance, which keeps features that matter only in interaction;
 ``PairScreen`` (``mutual_information.rank_pair_interactions``) scans all pairs
 for the ones that act purely together and returns them as a ranked list.
+``RReliefF`` scores features against a continuous target (the Relief
+estimators above read y as class labels), with a permutation test.
 
 Importing the package loads the native library; it fails loudly if the
 library has not been built.
@@ -28,6 +30,7 @@ from .mRMR import mRMR
 from .MultiSURF import MultiSURF
 from .PairScreen import PairScreen
 from .ReliefF import ReliefF
+from .RReliefF import RReliefF
 from .SURF import SURF
 from .star import MultiSURFstar, SURFstar
 from .TuRF import TuRF
@@ -37,12 +40,12 @@ from .TuRF import TuRF
 # attribute access cannot find them there and serialises the class by value:
 # dill does, and once a package that uses it (multiprocess, datasets) is
 # imported, so does joblib.dump.  Name the estimators by their public address.
-for _cls in (MultiSURF, ReliefF, SURF, TuRF, MDR, mRMR, CFS, JMI, PairScreen):
+for _cls in (MultiSURF, ReliefF, RReliefF, SURF, TuRF, MDR, mRMR, CFS, JMI, PairScreen):
     _cls.__module__ = __name__
 del _cls
 
 __version__ = "0.1.0"
-__all__ = ["ReliefF", "SURF", "MultiSURF", "SURFstar", "MultiSURFstar", "TuRF", "MDR", "mRMR",
+__all__ = ["ReliefF", "RReliefF", "SURF", "MultiSURF", "SURFstar", "MultiSURFstar", "TuRF", "MDR", "mRMR",
            "CFS", "JMI", "PairScreen"]
 
 

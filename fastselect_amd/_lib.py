@@ -63,6 +63,8 @@ EXPORTED = (
     "fs_plan_score_labels", "fs_multisurf_score_labels", "fs_plan_labels_kernel_ms",
     "fs_plan_relieff_score_labels", "fs_relieff_score_labels", "fs_plan_relieff_labels_info",
     "fs_plan_relieff_labels_kernel_ms",
+    "fs_plan_score_targets", "fs_rrelieff_scores", "fs_rrelieff_score",
+    "fs_plan_targets_kernel_ms",
     "fs_plan_star_split", "fs_plan_set_star_split", "fs_multisurf_last_star_split",
 )
 
@@ -174,6 +176,15 @@ def _load() -> ctypes.CDLL:
     lib.fs_plan_relieff_labels_info.restype = _int
     lib.fs_plan_relieff_labels_kernel_ms.argtypes = [_vp, _int]
     lib.fs_plan_relieff_labels_kernel_ms.restype = ctypes.c_double
+    lib.fs_plan_score_targets.argtypes = [_vp, _f64p, _i64, _vp, _vp, _vp]
+    lib.fs_plan_score_targets.restype = _int
+    lib.fs_rrelieff_scores.argtypes = [_f64p, _f64p, ctypes.c_double, ctypes.c_double, _i64, _f32p]
+    lib.fs_rrelieff_scores.restype = _int
+    lib.fs_rrelieff_score.argtypes = [_int, _int, _f32p, _i64, _i64, _f64p, _i64, _f32p, _u8p,
+                                      _i64, _int, _f32p]
+    lib.fs_rrelieff_score.restype = _int
+    lib.fs_plan_targets_kernel_ms.argtypes = [_vp, _int]
+    lib.fs_plan_targets_kernel_ms.restype = ctypes.c_double
     lib.fs_plan_decision_guard.argtypes = [_vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double),
                                            ctypes.POINTER(_int)]
     lib.fs_plan_ref_mask_words.argtypes = [_vp, _i64p]
@@ -633,6 +644,47 @@ def relieff_score_labels(backend, x, labels, recip, is_discrete, k, n_jobs=-1, d
     return out
 
 
+def _targets_arg(targets, n):
+    t = np.ascontiguousarray(targets, dtype=np.float64)
+    if t.ndim == 1:
+        t = t.reshape(1, -1)
+    if t.ndim != 2 or t.shape[1] != n:
+        raise ValueError(f"targets must have shape (B, {n}); got {t.shape}")
+    return t
+
+
+def rrelieff_scores(s_a, s_ca, s_c, n_pairs):
+    """The RReliefF epilogue (``fs_rrelieff_scores``) per target: float32
+    scores (B, n_kept) from S_A (n_kept), S_CA (B, n_kept), S_C (B) and the
+    number of pairs M = rows * k."""
+    s_a = np.ascontiguousarray(s_a, dtype=np.float64)
+    s_ca = np.ascontiguousarray(s_ca, dtype=np.float64).reshape(-1, s_a.size)
+    s_c = np.ascontiguousarray(s_c, dtype=np.float64).reshape(-1)
+    out = np.zeros(s_ca.shape, dtype=np.float32)
+    for b in range(s_ca.shape[0]):
+        check(_lib.fs_rrelieff_scores(_p(s_a, _f64p), _p(s_ca[b], _f64p), float(s_c[b]),
+                                      float(n_pairs), s_a.size, _p(out[b], _f32p)))
+    return out
+
+
+def rrelieff_score(backend, x, targets, recip, is_discrete, k, n_jobs=-1, device=0):
+    """RReliefF scores of B continuous targets of the same samples in one call
+    (``fs_rrelieff_score``): the neighbours (the k nearest of all) do not read
+    the target, so distances and selection run once and a target only adds a
+    weight per (sample, neighbour) pair.  ``targets``: (B, n) or (n,) float64,
+    finite.  Returns (B, p) float32."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n, p = x.shape
+    t = _targets_arg(targets, n)
+    rc_ = np.ascontiguousarray(recip, dtype=np.float32)
+    isd = np.ascontiguousarray(is_discrete, dtype=np.uint8)
+    out = np.zeros((t.shape[0], p), dtype=np.float32)
+    check(_lib.fs_rrelieff_score(_backend_code(backend), int(device), _p(x, _f32p), n, p,
+                                 _p(t, _f64p), t.shape[0], _p(rc_, _f32p), _p(isd, _u8p), int(k),
+                                 int(n_jobs), _p(out, _f32p)))
+    return out
+
+
 def relieff_score(backend, x, y_enc, recip, is_discrete, k, class_probs, n_jobs=-1, device=0,
                   rows=None, devices=None):
     """Drop-in for ``_relieff_{cpu,gpu}_host_caller`` (ReliefF.py:127-134, 222-236).
@@ -956,6 +1008,21 @@ class RowsPlan(Plan):
         prefix, walk and score kernels, 3 the general route's selection and
         update (``fs_plan_relieff_labels_kernel_ms``; -1: unavailable)."""
         return float(_lib.fs_plan_relieff_labels_kernel_ms(self._h, int(which)))
+
+    def score_targets(self, targets, s_a_ptr: int, s_ca_ptr: int, s_c_ptr: int) -> None:
+        """The RReliefF sums of the (B, n) float64 host targets on a one-class
+        ReliefF plan (``fs_plan_score_targets``): S_A into s_a[n_kept], S_CA
+        into s_ca[B * n_kept], S_C into s_c[B], all three in the memory space
+        ``score`` writes to.  Pass 1 and the selection run once per call."""
+        t = _targets_arg(targets, self.n)
+        check(_lib.fs_plan_score_targets(self._h, _p(t, _f64p), t.shape[0], _vp(s_a_ptr or None),
+                                         _vp(s_ca_ptr or None), _vp(s_c_ptr or None)))
+
+    def targets_kernel_ms(self, which: int) -> float:
+        """HIP-event time of the last ``score_targets``: 0 the selection, 1
+        the update kernel summed over the chunks of targets
+        (``fs_plan_targets_kernel_ms``; -1: unavailable)."""
+        return float(_lib.fs_plan_targets_kernel_ms(self._h, int(which)))
 
     def ref_temp(self) -> None:
         """Reference order: the score up to the float32 temp rows, whose column

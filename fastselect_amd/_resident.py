@@ -4,6 +4,7 @@ TuRF caller, TuRF.py:93-115): X is uploaded once into a ReliefF / SURF plan
 it with ``fs_plan_set_features`` instead of refitting on ``X[:, active]``.
 Per-column preprocessing (discreteness, ranges) does not depend on the other
 columns, so the subset's inputs are the full ones restricted to ``active``.
+``ResidentTargets`` does the same for RReliefF on a one-class ReliefF plan.
 """
 from __future__ import annotations
 
@@ -105,6 +106,73 @@ class ResidentRows:
         else:
             sums = self._sums(active.size)
         scores = (sums / self.n).astype(np.float32)
+        est.is_discrete_ = self.is_discrete[active]
+        est.feature_importances_ = scores
+        est.top_features_ = _base.top_features(scores, n_select)
+        return est
+
+    def close(self):
+        self.plan.close()
+
+
+class ResidentTargets:
+    """RReliefF on a resident one-class ReliefF plan: ``refit(active)`` leaves
+    ``est`` exactly as ``est.fit(X[:, active], y)`` would, and
+    ``score_targets(targets)`` scores any number of targets of the same
+    samples in one ``fs_plan_score_targets`` call (the neighbours do not read
+    the target, so distances and selection run once per call)."""
+
+    def __init__(self, est, plan: _lib.RowsPlan, n: int, k: int, y, is_discrete, backend: str):
+        self.est = est
+        self.plan = plan
+        self.n = n
+        self.k = k
+        self.y = np.ascontiguousarray(y, dtype=np.float64)
+        self.is_discrete = is_discrete
+        self.backend = backend
+        self.active = None
+
+    def sums(self, targets):
+        """(S_A (n_kept), S_CA (B, n_kept), S_C (B)) of the (B, n) targets on
+        the current feature subset."""
+        targets = np.ascontiguousarray(targets, dtype=np.float64)
+        if targets.ndim == 1:
+            targets = targets.reshape(1, -1)
+        B, n_kept = targets.shape[0], self.plan.n_kept
+        if self.backend == "gpu":
+            import torch
+            # torch.empty, no fill kernels: the plan clears its sums on its own
+            # (non-blocking) stream, which nothing torch queued is ordered
+            # before (ResidentRows._sums)
+            buf = torch.empty(n_kept + B * n_kept + B, dtype=torch.float64, device="cuda")
+            torch.cuda.current_stream().synchronize()
+            p0 = buf.data_ptr()
+            # synchronises the plan's stream
+            self.plan.score_targets(targets, p0, p0 + 8 * n_kept, p0 + 8 * (n_kept + B * n_kept))
+            out = buf.cpu().numpy()
+        else:
+            out = np.zeros(n_kept + B * n_kept + B, dtype=np.float64)
+            p0 = out.ctypes.data
+            self.plan.score_targets(targets, p0, p0 + 8 * n_kept, p0 + 8 * (n_kept + B * n_kept))
+        return (out[:n_kept], out[n_kept:n_kept + B * n_kept].reshape(B, n_kept),
+                out[n_kept + B * n_kept:])
+
+    def score_targets(self, targets) -> np.ndarray:
+        """The (B, n_kept) float32 RReliefF scores of the (B, n) targets."""
+        s_a, s_ca, s_c = self.sums(targets)
+        return _lib.rrelieff_scores(s_a, s_ca, s_c, float(self.n) * float(self.k))
+
+    def refit(self, active):
+        est = self.est
+        active = np.asarray(active, dtype=np.int64)
+        n_select = est._validate_parameters(self.n, active.size)
+        est.n_features_in_ = active.size
+        if est.verbose:
+            print(f"Running RReliefF on the {self.backend.upper()} now...")
+        if self.active is None or not np.array_equal(active, self.active):
+            self.plan.set_features(active)
+            self.active = active
+        scores = self.score_targets(self.y)[0]
         est.is_discrete_ = self.is_discrete[active]
         est.feature_importances_ = scores
         est.top_features_ = _base.top_features(scores, n_select)

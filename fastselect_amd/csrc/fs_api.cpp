@@ -14,6 +14,7 @@
 #include "fs_mi.h"
 #include "fs_mrmr.h"
 #include "fs_pairscan.h"
+#include "fs_rrelieff.h"
 #include "fs_stir.h"
 
 #include <chrono>
@@ -1121,6 +1122,101 @@ int fs_plan_relieff_labels_info(const fs_plan* pl, int64_t out[4]) {
 double fs_plan_relieff_labels_kernel_ms(const fs_plan* pl, int which) {
   if (!pl || !pl->g) return -1.0;
   return gpu::plan_relieff_labels_kernel_ms(pl->g, which);
+}
+
+// ---- RReliefF (fs_rrelieff.h) ------------------------------------------------
+
+int fs_plan_score_targets(fs_plan* pl, const double* targets, int64_t B, double* s_a,
+                          double* s_ca, double* s_c) {
+  if (!pl || !targets || !s_a || !s_ca || !s_c) {
+    set_error("fs_plan_score_targets: NULL plan or buffer");
+    return FS_EINVAL;
+  }
+  if (B < 1) {
+    set_error("fs_plan_score_targets: B < 1");
+    return FS_EINVAL;
+  }
+  if (pl->P.algo != ALGO_RELIEFF) {
+    set_error("fs_plan_score_targets: a ReliefF plan with one class (not a SURF or MultiSURF "
+              "plan)");
+    return FS_EINVAL;
+  }
+  if (pl->P.n_classes != 1) {
+    set_error("fs_plan_score_targets: the plan has more than one class (RReliefF's neighbours "
+              "are the k nearest of all: create the plan with n_classes = 1)");
+    return FS_EINVAL;
+  }
+  if (pl->P.ref_accum) {
+    set_error("fs_plan_score_targets: not built for reference-order accumulation");
+    return FS_EINVAL;
+  }
+  if (pl->P.k_neighbors < 1 || pl->P.k_neighbors > pl->P.n - 1) {
+    set_error("fs_plan_score_targets: k must satisfy 1 <= k <= n - 1");
+    return FS_EINVAL;
+  }
+  std::vector<double> u;
+  if (const int64_t bad = rrelieff::scale_targets(targets, B, pl->P.n, u); bad >= 0) {
+    set_error("fs_plan_score_targets: target " + std::to_string(bad) +
+              " holds a non-finite value");
+    return FS_EINVAL;
+  }
+  if (pl->g) return gpu::plan_score_targets(pl->g, u.data(), B, s_a, s_ca, s_c);
+  return cpu::rrelieff_sums(pl->P, (const float*)pl->xp(), pl->n_jobs, pl->r_lo, pl->r_hi,
+                            u.data(), B, s_a, s_ca, s_c);
+}
+
+int fs_rrelieff_scores(const double* s_a, const double* s_ca_row, double s_c, double n_pairs,
+                       int64_t n_kept, float* scores) {
+  if (n_kept < 0 || (n_kept > 0 && (!s_a || !s_ca_row || !scores))) {
+    set_error("fs_rrelieff_scores: NULL buffer or n_kept < 0");
+    return FS_EINVAL;
+  }
+  rrelieff::scores(s_a, s_ca_row, s_c, n_pairs, n_kept, scores);
+  return FS_OK;
+}
+
+int fs_rrelieff_score(int backend, int device, const float* x, int64_t n, int64_t p,
+                      const double* targets, int64_t B, const float* recip,
+                      const uint8_t* is_discrete, int64_t k, int n_jobs, float* scores_out) {
+  if (!scores_out || !targets || B < 1) {
+    set_error("fs_rrelieff_score: need targets, scores_out and B >= 1");
+    return FS_EINVAL;
+  }
+  if (k < 1 || k > n - 1) {
+    set_error("fs_rrelieff_score: k must satisfy 1 <= k <= n - 1");
+    return FS_EINVAL;
+  }
+  int rc = check_backend(backend, device);
+  if (rc != FS_OK) return rc;
+  Prepared P;
+  rc = prepare(P, ALGO_RELIEFF, x, 0, n, p, nullptr, p, recip, is_discrete, n_jobs,
+               backend == FS_BACKEND_GPU);
+  if (rc) return map_prep_rc(rc);
+  P.labels.assign((size_t)n, 0);
+  P.n_classes = 1;
+  P.class_prior.assign(1, 1.0);
+  P.k_neighbors = k;
+  // fast accumulation whatever the process-wide mode: P.ref_accum stays 0
+  std::vector<double> u;
+  if (const int64_t bad = rrelieff::scale_targets(targets, B, n, u); bad >= 0) {
+    set_error("fs_rrelieff_score: target " + std::to_string(bad) + " holds a non-finite value");
+    return FS_EINVAL;
+  }
+  if (backend == FS_BACKEND_GPU) return gpu::rrelieff_run(P, x, device, u.data(), B, scores_out);
+  const int64_t nk = P.n_kept;
+  std::vector<double> sa((size_t)nk), sca((size_t)(B * nk)), sc((size_t)B);
+  if ((rc = cpu::rrelieff_sums(P, x, n_jobs, 0, n, u.data(), B, sa.data(), sca.data(),
+                               sc.data())) != FS_OK)
+    return rc;
+  for (int64_t b = 0; b < B; b++)
+    rrelieff::scores(sa.data(), sca.data() + b * nk, sc[b], (double)n * (double)k, nk,
+                     scores_out + b * nk);
+  return FS_OK;
+}
+
+double fs_plan_targets_kernel_ms(const fs_plan* pl, int which) {
+  if (!pl || !pl->g) return -1.0;
+  return gpu::plan_targets_kernel_ms(pl->g, which);
 }
 
 int fs_plan_pass2(fs_plan* pl, const double* counts, double* scores) {

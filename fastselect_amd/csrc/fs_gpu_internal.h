@@ -16,6 +16,7 @@
 //   fs_devices.hip   single-process multi-GPU (the estimators' devices=)
 //   fs_stir.hip      STIR: hit / miss sums of diff and diff^2 over the near pairs
 //   fs_stir_relieff.hip  the same sums over ReliefF's neighbour lists
+//   fs_rrelieff.hip  RReliefF: the sums of a one-class ReliefF plan per target
 //   fs_labels.hip    MultiSURF permutation test: many labellings on one plan's decisions
 //   fs_relieff_labels.hip  ReliefF permutation test: many labellings on one pass 1
 //
@@ -269,6 +270,12 @@ struct Plan {
   double rf_labels_ms[4] = {0, 0, 0, 0};
   hipEvent_t ev_rf_labels[2] = {nullptr, nullptr};
   hipEvent_t ev_rf_fast[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // plan_score_targets (fs_rrelieff.hip): the selection's start / stop events
+  // and per chunk of targets k_rrf_update's (plan_targets_kernel_ms), taken
+  // on demand; rrf_chunks: chunks the last completed call walked (-1: none)
+  hipEvent_t ev_rrf_sel[2] = {nullptr, nullptr};
+  std::vector<hipEvent_t> ev_rrf;
+  int rrf_chunks = -1;
   DevArena mem_plan{device};    // buffers sized by n (live as long as the plan)
   DevArena mem_layout{device};  // buffers sized by the feature layout (PW)
   DevArena mem_shard{device};   // buffers sized by the owned tiles (plan_set_shard)
@@ -420,6 +427,10 @@ int relieff_update_fold(Plan* g, const double* dprior, const int32_t* nbr, const
                         double* part, double* sums_dev);
 int relieff_select_update(Plan* g, const int64_t* dcc, const double* dprior, int32_t* nbr,
                           int32_t* nfound, double* part, double* sums_dev);
+// The selection alone, on resident distances (run_quantize_dist): the lists
+// nbr[n][C][k] / nfound[n][C] of the plan's focal rows, dcc the class counts
+// on the device (fs_rrelieff.hip scores targets on a one-class plan's lists).
+int relieff_select(Plan* g, const int64_t* dcc, int32_t* nbr, int32_t* nfound);
 // Exact float32 keys of whole rows (drows on the device) into keys[nr][n],
 // +inf at the focal sample; and numba's order for the runs of equal keys in
 // the candidate prefixes cand[i][0..lok[i]) (L per row, sorted keys ckeys) of

@@ -15,6 +15,8 @@ void plan_destroy(Plan* g) {
   for (auto& e : g->ev) event_put(g->device, e, true);
   for (auto& e : g->ev_stir) event_put(g->device, e, true);
   for (auto& e : g->ev_rf_stir) event_put(g->device, e, true);
+  for (auto& e : g->ev_rrf_sel) event_put(g->device, e, true);
+  for (auto& e : g->ev_rrf) event_put(g->device, e, true);
   for (auto& e : g->ev_labels) event_put(g->device, e, true);
   for (auto& e : g->ev_rf_labels) event_put(g->device, e, true);
   for (auto& e : g->ev_rf_fast) event_put(g->device, e, true);

@@ -1513,7 +1513,7 @@ __global__ __launch_bounds__(256) void k_rf_update(const float* __restrict__ xs,
 // ReliefF neighbour selection on the resident distances: quantised keys,
 // exact reference keys for every candidate near a class's k-th key, exact
 // selection, then numba's quicksort order for rows with ties at the k-th key.
-static int relieff_select(Plan* g, const int64_t* dcc, int32_t* nbr, int32_t* nfound) {
+int relieff_select(Plan* g, const int64_t* dcc, int32_t* nbr, int32_t* nfound) {
   const Prepared& Q = g->P;
   const int C = Q.n_classes;
   const int64_t k = Q.k_neighbors, n = Q.n;

@@ -551,6 +551,47 @@ FS_API int fs_relieff_score_labels(int backend, int device, const float* x, int6
                                    float* scores_out);
 FS_API int fs_plan_relieff_labels_info(const fs_plan* plan, int64_t out[4]);
 FS_API double fs_plan_relieff_labels_kernel_ms(const fs_plan* plan, int which);
+/* RReliefF: Relief for continuous targets (definitions: csrc/fs_rrelieff.h).
+ * The neighbours of a focal sample are its k nearest other samples -- the
+ * lists of a ReliefF plan with ONE class (fs_plan_create_relieff with
+ * n_classes = 1, y_enc all 0, class_probs = {1}) -- and do not read the
+ * target, so the distance pass and the selection run once per call for any
+ * number of targets.
+ *
+ * fs_plan_score_targets: for the B targets targets[b * n + i] (host memory,
+ * float64, finite) the raw sums over the (focal row, neighbour) pairs of the
+ * plan's focal rows and current feature subset: s_a[n_kept] = sum of diff,
+ * s_ca[b * n_kept + f] = sum of dy_b * diff, s_c[b] = sum of dy_b, with
+ * dy_b(i, j) = |t_i - t_j| / (max t - min t) of target b (0 for a constant
+ * target).  Outputs in the memory space fs_plan_score writes to.  The sums add
+ * up over disjoint focal-row ranges; the number of pairs is rows * k.  Row b
+ * of any call has the bits of the B = 1 call of target b, s_a the same bits
+ * for any B, and a repeated call gives the same bits (no float atomics).
+ * FS_EINVAL, with nothing written: a NULL pointer, B < 1, a non-finite target,
+ * a plan with more than one class, a SURF or MultiSURF plan, a plan in
+ * reference-order accumulation, k < 1 or k > n - 1.  An empty row range gives
+ * zeros.
+ *
+ * fs_rrelieff_scores: the epilogue on the host, for one target:
+ * scores[f] = s_ca[f] / s_c - (s_a[f] - s_ca[f]) / (n_pairs - s_c) in float64,
+ * rounded to float32; all 0 when s_c == 0 or s_c == n_pairs.
+ *
+ * fs_rrelieff_score: one call from host arrays (every column scored, fast
+ * accumulation); scores_out[b * p + f].
+ *
+ * fs_plan_targets_kernel_ms: HIP-event time in milliseconds of the last
+ * completed fs_plan_score_targets (GPU only; -1 when unavailable).  which:
+ * 0 = the neighbour selection, 1 = the update kernel, summed over the chunks
+ * of targets. */
+FS_API int fs_plan_score_targets(fs_plan* plan, const double* targets, int64_t B, double* s_a,
+                                 double* s_ca, double* s_c);
+FS_API int fs_rrelieff_scores(const double* s_a, const double* s_ca_row, double s_c,
+                              double n_pairs, int64_t n_kept, float* scores);
+FS_API int fs_rrelieff_score(int backend, int device, const float* x, int64_t n, int64_t p,
+                             const double* targets, int64_t B, const float* recip,
+                             const uint8_t* is_discrete, int64_t k, int n_jobs,
+                             float* scores_out);
+FS_API double fs_plan_targets_kernel_ms(const fs_plan* plan, int which);
 /* After the three stages of a MultiSURF step, with rowstats[3n], counts[2n]
  * and scores[n_kept] all-reduced (identical on every rank): the 16-bit
  * decision check of fs_multisurf_score (see fs_multisurf_last_guard) for
