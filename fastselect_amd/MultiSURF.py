@@ -285,20 +285,7 @@ class MultiSURF(TransformerMixin, BaseEstimator):
             scores = scorer.job.score_labels(labels).cpu().numpy().astype(np.float64)
         finally:
             scorer.close()
-        obs, null = scores[0], scores[1:]
-        null_max = null.max(axis=1)
-        self.n_permutations_ = n_permutations
-        self.p_values_ = (1.0 + (null >= obs[None, :]).sum(axis=0)) / (1.0 + n_permutations)
-        self.p_values_maxT_ = ((1.0 + (null_max[:, None] >= obs[None, :]).sum(axis=0))
-                               / (1.0 + n_permutations))
-        self.null_max_scores_ = null_max
-        self.null_mean_ = null.mean(axis=0)
-        self.null_std_ = null.std(axis=0)
-        if keep_null:
-            self.null_scores_ = null
-        elif hasattr(self, "null_scores_"):
-            del self.null_scores_
-        return self
+        return _base.set_permutation_attributes(self, scores, n_permutations, keep_null)
 
     def _resident_scorer(self, x, y):
         """A scorer for TuRF that keeps X resident (on the GPU for the GPU

@@ -291,20 +291,7 @@ class ReliefF(TransformerMixin, BaseEstimator):
         finally:
             scorer.close()
         scores = (sums / scorer.n).astype(np.float32).astype(np.float64)
-        obs, null = scores[0], scores[1:]
-        null_max = null.max(axis=1)
-        self.n_permutations_ = n_permutations
-        self.p_values_ = (1.0 + (null >= obs[None, :]).sum(axis=0)) / (1.0 + n_permutations)
-        self.p_values_maxT_ = ((1.0 + (null_max[:, None] >= obs[None, :]).sum(axis=0))
-                               / (1.0 + n_permutations))
-        self.null_max_scores_ = null_max
-        self.null_mean_ = null.mean(axis=0)
-        self.null_std_ = null.std(axis=0)
-        if keep_null:
-            self.null_scores_ = null
-        elif hasattr(self, "null_scores_"):
-            del self.null_scores_
-        return self
+        return _base.set_permutation_attributes(self, scores, n_permutations, keep_null)
 
     def transform(self, x: np.ndarray) -> np.ndarray:
         """Reduce x to the selected features."""

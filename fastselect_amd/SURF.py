@@ -145,6 +145,60 @@ class SURF(TransformerMixin, BaseEstimator):
         return ResidentRows(self, "SURF*" if self.use_star else "SURF", plan, n, is_discrete,
                             self.effective_backend_)
 
+    def permutation_test(self, X: np.ndarray, y: np.ndarray, n_permutations=1000,
+                         random_state=None, keep_null=False):
+        """Score every feature on the resident plan and give each score a
+        permutation p-value: y itself and ``n_permutations`` uniform
+        permutations of it (drawn from ``np.random.default_rng(random_state)``)
+        are scored in one ``score_labels`` call (``fs_plan_surf_score_labels``).
+        SURF's near sets do not read the labels, so distances, their float32
+        resolution and the means run once; a labelling re-weighs the near pairs
+        (+-1 a side) and, for SURF*, walks every sorted column once.  Row 0 of
+        that call is y, so the observed scores and the null share one
+        arithmetic.
+
+        Sets the attributes the resident scorer's ``refit`` sets
+        (``feature_importances_``, ``top_features_``, ...) and ``p_values_``,
+        ``p_values_maxT_``, ``null_max_scores_``, ``null_mean_``,
+        ``null_std_``, ``n_permutations_`` and, with ``keep_null=True``,
+        ``null_scores_`` -- defined exactly as ``ReliefF.permutation_test``
+        defines them.  The resident plan runs on device 0 (``devices_`` says
+        so).  ValueError for a single class, for ``accumulation='reference'``,
+        for ``n_permutations < 1`` and when ``devices`` names more than one
+        device.  On the GPU SURF* takes at most 8 classes and 24576 samples."""
+        _lib.accumulation_code(self.accumulation)
+        if self.accumulation != "fast":
+            raise ValueError("the permutation test runs in accumulation='fast' (the null is not "
+                             "accumulated in reference order)")
+        n_permutations = int(n_permutations)
+        if n_permutations < 1:
+            raise ValueError(f"n_permutations must be >= 1; got {n_permutations}")
+        devs = _base.fit_devices(self.devices, _base.effective_backend(self.backend),
+                                 _base.rows_hint(X) or 0)
+        if devs is not None and len(devs) > 1:
+            raise ValueError("SURF.permutation_test runs on one device; got "
+                             f"devices={list(devs)!r}")
+        y_enc = np.unique(np.asarray(y).reshape(-1), return_inverse=True)[1]
+        y_enc = y_enc.astype(np.int32).reshape(-1)
+        if y_enc.size and int(y_enc.max()) < 1:
+            raise ValueError("a permutation of y is y itself: y has a single class")
+        scorer = self._resident_scorer(X, y)  # validates X and y as fit does
+        try:
+            self.devices_ = [0] if self.effective_backend_ == "gpu" else None
+            # a new plan scores every column: nothing to re-target
+            scorer.active = np.arange(scorer.is_discrete.size, dtype=np.int64)
+            scorer.refit(scorer.active)
+            rng = np.random.default_rng(random_state)
+            labels = np.empty((n_permutations + 1, y_enc.size), dtype=np.int32)
+            labels[0] = y_enc
+            for b in range(n_permutations):
+                labels[b + 1] = rng.permutation(y_enc)
+            sums = scorer.score_labels(labels)
+        finally:
+            scorer.close()
+        scores = (sums / scorer.n).astype(np.float32).astype(np.float64)
+        return _base.set_permutation_attributes(self, scores, n_permutations, keep_null)
+
     def transform(self, x: np.ndarray) -> np.ndarray:
         """Reduce x to the selected features."""
         check_is_fitted(self)

@@ -234,3 +234,27 @@ def top_features(scores: np.ndarray, n_select: int) -> np.ndarray:
     """``np.argsort(scores)[::-1][:n_select]`` (MultiSURF.py:443): numpy's own
     argsort on the float32 scores, so ties order exactly as the reference."""
     return np.argsort(scores)[::-1][:n_select]
+
+
+def set_permutation_attributes(est, scores, n_permutations: int, keep_null: bool):
+    """The permutation tests' epilogue (MultiSURF, ReliefF, SURF): ``scores``
+    is (1 + n_permutations, n_features) float64 with row 0 the observed scores
+    and the rest the null.  Sets ``p_values_`` ((1 + #{null_f >= obs_f}) /
+    (1 + n_permutations)), ``p_values_maxT_`` (Westfall-Young: the same against
+    each permutation's largest score), ``null_max_scores_``, ``null_mean_``,
+    ``null_std_``, ``n_permutations_`` and, with ``keep_null``,
+    ``null_scores_`` (removed otherwise)."""
+    obs, null = scores[0], scores[1:]
+    null_max = null.max(axis=1)
+    est.n_permutations_ = n_permutations
+    est.p_values_ = (1.0 + (null >= obs[None, :]).sum(axis=0)) / (1.0 + n_permutations)
+    est.p_values_maxT_ = ((1.0 + (null_max[:, None] >= obs[None, :]).sum(axis=0))
+                          / (1.0 + n_permutations))
+    est.null_max_scores_ = null_max
+    est.null_mean_ = null.mean(axis=0)
+    est.null_std_ = null.std(axis=0)
+    if keep_null:
+        est.null_scores_ = null
+    elif hasattr(est, "null_scores_"):
+        del est.null_scores_
+    return est

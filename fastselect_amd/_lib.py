@@ -63,6 +63,8 @@ EXPORTED = (
     "fs_plan_score_labels", "fs_multisurf_score_labels", "fs_plan_labels_kernel_ms",
     "fs_plan_relieff_score_labels", "fs_relieff_score_labels", "fs_plan_relieff_labels_info",
     "fs_plan_relieff_labels_kernel_ms",
+    "fs_plan_surf_score_labels", "fs_surf_score_labels", "fs_plan_surf_labels_info",
+    "fs_plan_surf_labels_kernel_ms",
     "fs_plan_score_targets", "fs_rrelieff_scores", "fs_rrelieff_score",
     "fs_plan_targets_kernel_ms",
     "fs_plan_star_split", "fs_plan_set_star_split", "fs_multisurf_last_star_split",
@@ -176,6 +178,15 @@ def _load() -> ctypes.CDLL:
     lib.fs_plan_relieff_labels_info.restype = _int
     lib.fs_plan_relieff_labels_kernel_ms.argtypes = [_vp, _int]
     lib.fs_plan_relieff_labels_kernel_ms.restype = ctypes.c_double
+    lib.fs_plan_surf_score_labels.argtypes = [_vp, _i32p, _i64, _vp]
+    lib.fs_plan_surf_score_labels.restype = _int
+    lib.fs_surf_score_labels.argtypes = [_int, _int, _f64p, _i64, _i64, _i32p, _i64, _f32p,
+                                         _u8p, _int, _int, _f32p]
+    lib.fs_surf_score_labels.restype = _int
+    lib.fs_plan_surf_labels_info.argtypes = [_vp, _i64p]
+    lib.fs_plan_surf_labels_info.restype = _int
+    lib.fs_plan_surf_labels_kernel_ms.argtypes = [_vp, _int]
+    lib.fs_plan_surf_labels_kernel_ms.restype = ctypes.c_double
     lib.fs_plan_score_targets.argtypes = [_vp, _f64p, _i64, _vp, _vp, _vp]
     lib.fs_plan_score_targets.restype = _int
     lib.fs_rrelieff_scores.argtypes = [_f64p, _f64p, ctypes.c_double, ctypes.c_double, _i64, _f32p]
@@ -644,6 +655,26 @@ def relieff_score_labels(backend, x, labels, recip, is_discrete, k, n_jobs=-1, d
     return out
 
 
+def surf_score_labels(backend, x, labels, recip, is_discrete, use_star=False, n_jobs=-1, device=0):
+    """SURF / SURF* scores of B labellings of the same samples in one call
+    (``fs_surf_score_labels``): the near sets do not read the labels, so
+    distances and means run once and every labelling only re-weighs the near
+    pairs (SURF*: and walks each sorted column).  ``labels``: (B, n) integers,
+    compared by equality only (GPU, SURF*: codes in [0, 8)).  Returns (B, p)
+    float32; row b is the score vector of ``surf_score`` with labelling b as y
+    (CPU backend: bit for bit)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    n, p = x.shape
+    lab = _labels_arg(labels, n)
+    rc_ = np.ascontiguousarray(recip, dtype=np.float32)
+    isd = np.ascontiguousarray(is_discrete, dtype=np.uint8)
+    out = np.zeros((lab.shape[0], p), dtype=np.float32)
+    check(_lib.fs_surf_score_labels(_backend_code(backend), int(device), _p(x, _f64p), n, p,
+                                    _p(lab, _i32p), lab.shape[0], _p(rc_, _f32p), _p(isd, _u8p),
+                                    int(bool(use_star)), int(n_jobs), _p(out, _f32p)))
+    return out
+
+
 def _targets_arg(targets, n):
     t = np.ascontiguousarray(targets, dtype=np.float64)
     if t.ndim == 1:
@@ -948,6 +979,7 @@ class RowsPlan(Plan):
                  use_star=False, rows=None, n_jobs=-1, device=0, stream=0):
         super().__init__(None, None, None, None, None, _handle=True)
         self.backend = backend
+        self.algo = algo
         self._h = _vp()
         rc_ = np.ascontiguousarray(recip, dtype=np.float32)
         isd = np.ascontiguousarray(is_discrete, dtype=np.uint8)
@@ -1008,6 +1040,30 @@ class RowsPlan(Plan):
         prefix, walk and score kernels, 3 the general route's selection and
         update (``fs_plan_relieff_labels_kernel_ms``; -1: unavailable)."""
         return float(_lib.fs_plan_relieff_labels_kernel_ms(self._h, int(which)))
+
+    def surf_score_labels(self, labels, scores_ptr: int) -> None:
+        """The SURF / SURF* score sums (as the plan's ``use_star``) of the
+        (B, n) int32 host labellings into scores[B * n_kept]
+        (``fs_plan_surf_score_labels``): distances, means and the near pairs
+        once, then weights and score per chunk of labellings; scores in the
+        memory space ``score`` writes to.  A later ``score`` is unchanged."""
+        lab = _labels_arg(labels, self.n)
+        check(_lib.fs_plan_surf_score_labels(self._h, _p(lab, _i32p), lab.shape[0],
+                                             _vp(scores_ptr or None)))
+
+    def surf_labels_info(self):
+        """(weighted pairs listed, near sides, chunks walked, 1 if the star
+        walk ran) of the last ``surf_score_labels``
+        (``fs_plan_surf_labels_info``)."""
+        v = np.zeros(4, dtype=np.int64)
+        check(_lib.fs_plan_surf_labels_info(self._h, _p(v, _i64p)))
+        return tuple(int(q) for q in v)
+
+    def surf_labels_kernel_ms(self, which: int) -> float:
+        """HIP-event time of the last ``surf_score_labels``: 0 distances +
+        resolve + records, 1 weights, 2 the score kernel, 3 column sort + star
+        walk (``fs_plan_surf_labels_kernel_ms``; -1: unavailable)."""
+        return float(_lib.fs_plan_surf_labels_kernel_ms(self._h, int(which)))
 
     def score_targets(self, targets, s_a_ptr: int, s_ca_ptr: int, s_c_ptr: int) -> None:
         """The RReliefF sums of the (B, n) float64 host targets on a one-class

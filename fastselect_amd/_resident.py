@@ -69,9 +69,12 @@ class ResidentRows:
         return sums, stir.reshape(4, n_kept), int(counts[0]), int(counts[1])
 
     def score_labels(self, labels) -> np.ndarray:
-        """One ``fs_plan_relieff_score_labels`` call on the current feature
-        subset (a ReliefF plan): the (B, n_kept) float64 score sums of the
-        (B, n) labellings, class codes in [0, 64)."""
+        """One labellings call on the current feature subset: the (B, n_kept)
+        float64 score sums of the (B, n) labellings.  A ReliefF plan:
+        ``fs_plan_relieff_score_labels``, class codes in [0, 64); a SURF plan:
+        ``fs_plan_surf_score_labels``."""
+        if self.plan.algo == "surf":
+            return self._surf_score_labels(labels)
         labels = np.ascontiguousarray(labels, dtype=np.int32)
         if labels.ndim == 1:
             labels = labels.reshape(1, -1)
@@ -85,6 +88,22 @@ class ResidentRows:
             return out[:B * n_kept].cpu().numpy().reshape(B, n_kept)
         out = np.zeros((B, n_kept), dtype=np.float64)
         self.plan.score_labels(labels, out.ctypes.data)
+        return out
+
+    def _surf_score_labels(self, labels) -> np.ndarray:
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.ndim == 1:
+            labels = labels.reshape(1, -1)
+        B, n_kept = labels.shape[0], self.plan.n_kept
+        if self.backend == "gpu":
+            import torch
+            # torch.empty, no fill kernels, and the same ordering as _sums
+            out = torch.empty(max(B * n_kept, 1), dtype=torch.float64, device="cuda")
+            torch.cuda.current_stream().synchronize()
+            self.plan.surf_score_labels(labels, out.data_ptr())  # synchronises the plan's stream
+            return out[:B * n_kept].cpu().numpy().reshape(B, n_kept)
+        out = np.zeros((B, n_kept), dtype=np.float64)
+        self.plan.surf_score_labels(labels, out.ctypes.data)
         return out
 
     def refit(self, active, stir=False):

@@ -178,6 +178,7 @@ int fs_test_hook(const char* name, int64_t value) {
   else if (k == "stir_seg_len") h.stir_seg_len = value;
   else if (k == "labels_chunk") h.labels_chunk = value;
   else if (k == "labels_seg_len") h.labels_seg_len = value;
+  else if (k == "star_lab_seg") h.star_lab_seg = value;
   else if (k == "rf_labels_route") h.rf_labels_route = value;
   else if (k == "rf_labels_depth") h.rf_labels_depth = value;
   else if (k == "rf_labels_depth_cap") h.rf_labels_depth_cap = value;
@@ -694,6 +695,9 @@ struct fs_plan {
   // labellings of the last completed fs_plan_relieff_score_labels on the CPU
   // backend (-1: none; the GPU plan keeps its own record)
   int64_t rf_labels_done = -1;
+  // fs_plan_surf_labels_info of the last completed fs_plan_surf_score_labels
+  // on the CPU backend ([0] < 0: none)
+  int64_t surf_labels_info[4] = {-1, 0, 0, 0};
   Prepared P;
   Prepared P0;                  // as created (all columns): discrete tables for re-targeting
   gpu::Plan* g = nullptr;
@@ -1012,8 +1016,8 @@ int fs_plan_score_labels(fs_plan* pl, const int32_t* labels, int64_t B, double* 
     return FS_EINVAL;
   }
   if (pl->P.algo != ALGO_MULTISURF) {
-    set_error("fs_plan_score_labels: a MultiSURF plan (ReliefF's neighbours depend on the "
-              "labels; SURF is not built)");
+    set_error("fs_plan_score_labels: a MultiSURF plan (ReliefF: fs_plan_relieff_score_labels; "
+              "SURF: fs_plan_surf_score_labels)");
     return FS_EINVAL;
   }
   if (pl->P.use_star) {
@@ -1053,7 +1057,7 @@ int fs_plan_relieff_score_labels(fs_plan* pl, const int32_t* labels, int64_t B, 
   }
   if (pl->P.algo != ALGO_RELIEFF) {
     set_error("fs_plan_relieff_score_labels: a ReliefF plan (MultiSURF: fs_plan_score_labels; "
-              "SURF is not built)");
+              "SURF: fs_plan_surf_score_labels)");
     return FS_EINVAL;
   }
   if (pl->P.ref_accum) {
@@ -1122,6 +1126,80 @@ int fs_plan_relieff_labels_info(const fs_plan* pl, int64_t out[4]) {
 double fs_plan_relieff_labels_kernel_ms(const fs_plan* pl, int which) {
   if (!pl || !pl->g) return -1.0;
   return gpu::plan_relieff_labels_kernel_ms(pl->g, which);
+}
+
+int fs_plan_surf_score_labels(fs_plan* pl, const int32_t* labels, int64_t B, double* scores) {
+  if (!pl || B < 0 || (B > 0 && (!labels || !scores))) {
+    set_error("fs_plan_surf_score_labels: NULL plan or buffer, or B < 0");
+    return FS_EINVAL;
+  }
+  if (pl->P.algo != ALGO_SURF) {
+    set_error("fs_plan_surf_score_labels: a SURF plan (MultiSURF: fs_plan_score_labels; ReliefF: "
+              "fs_plan_relieff_score_labels)");
+    return FS_EINVAL;
+  }
+  if (pl->P.ref_accum) {
+    set_error("fs_plan_surf_score_labels: not built for reference-order accumulation");
+    return FS_ENOTSUP;
+  }
+  if (pl->world != 1 || pl->r_lo != 0 || pl->r_hi != pl->P.n) {
+    set_error("fs_plan_surf_score_labels: the plan must own every focal row [0, n) (world 1)");
+    return FS_ENOTSUP;
+  }
+  if (B == 0) return FS_OK;
+  pl->surf_labels_info[0] = -1;
+  if (pl->g) return gpu::plan_surf_score_labels(pl->g, labels, B, scores);
+  int64_t info[4];
+  const int rc = cpu::surf_score_labels(pl->P, pl->xp(), labels, B, pl->n_jobs, scores, info);
+  if (rc == FS_OK) std::copy(info, info + 4, pl->surf_labels_info);
+  return rc;
+}
+
+int fs_surf_score_labels(int backend, int device, const double* x, int64_t n, int64_t p,
+                         const int32_t* labels, int64_t B, const float* recip,
+                         const uint8_t* is_discrete, int use_star, int n_jobs,
+                         float* scores_out) {
+  if (!scores_out || !labels || B < 1) {
+    set_error("fs_surf_score_labels: need labels, scores_out and B >= 1");
+    return FS_EINVAL;
+  }
+  int rc = check_backend(backend, device);
+  if (rc != FS_OK) return rc;
+  Prepared P;
+  rc = prepare(P, ALGO_SURF, x, 1, n, p, nullptr, p, recip, is_discrete, n_jobs,
+               backend == FS_BACKEND_GPU);
+  if (rc) return map_prep_rc(rc);
+  if (encode_labels_i32(P, labels)) return FS_EINVAL;  // labelling 0 is the plan's y
+  P.use_star = use_star ? 1 : 0;
+  if ((rc = apply_accumulation(P)) != FS_OK) return rc;
+  if (P.ref_accum) {
+    set_error("fs_surf_score_labels: not built for reference-order accumulation");
+    return FS_ENOTSUP;
+  }
+  if (backend == FS_BACKEND_GPU) return gpu::surf_labels_run(P, x, device, labels, B, scores_out);
+  std::vector<double> S((size_t)B * P.n_kept);
+  if ((rc = cpu::surf_score_labels(P, x, labels, B, n_jobs, S.data())) != FS_OK) return rc;
+  for (int64_t q = 0; q < B * P.n_kept; q++) scores_out[q] = (float)(S[q] / (double)n);
+  return FS_OK;
+}
+
+int fs_plan_surf_labels_info(const fs_plan* pl, int64_t out[4]) {
+  if (!pl || !out) {
+    set_error("fs_plan_surf_labels_info: NULL plan or buffer");
+    return FS_EINVAL;
+  }
+  if (pl->g) return gpu::plan_surf_labels_info(pl->g, out);
+  if (pl->surf_labels_info[0] < 0) {
+    set_error("fs_plan_surf_labels_info: no completed fs_plan_surf_score_labels call");
+    return FS_EINVAL;
+  }
+  std::copy(pl->surf_labels_info, pl->surf_labels_info + 4, out);
+  return FS_OK;
+}
+
+double fs_plan_surf_labels_kernel_ms(const fs_plan* pl, int which) {
+  if (!pl || !pl->g) return -1.0;
+  return gpu::plan_surf_labels_kernel_ms(pl->g, which);
 }
 
 // ---- RReliefF (fs_rrelieff.h) ------------------------------------------------

@@ -535,16 +535,18 @@ int multisurf_pass2(const Prepared& P, const void* x, const CpuState& S, const d
   return FS_OK;
 }
 
-int surf_run(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t r_hi,
-             double* scores) {
+// What surf_run computes before it reads a label: the pass-2 operands, the
+// float32 distances and the focal rows' means.
+void surf_shared(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t r_hi,
+                 SurfShared& S) {
   // SURF compares float32-rounded distances with a float32 sequential mean,
   // so distances are accumulated in float64 from float64 diffs (as
   // k_dist_f64 does; exact to ~1e-16, SURF.py:146-160) rather than quantised.
   std::vector<uint32_t> xq;
-  std::vector<float> xs;
-  quantize(P, x, 1, n_jobs, xq, xs, nullptr);
+  quantize(P, x, 1, n_jobs, xq, S.xs, nullptr);
   const int64_t n = P.n;
-  std::vector<float> Df((size_t)n * n, 0.0f);
+  std::vector<float>& Df = S.Df;
+  Df.assign((size_t)n * n, 0.0f);
   parallel_for(n, n_jobs, [&](int64_t i) {
     for (int64_t j = i + 1; j < n; j++) {
       const float d = (float)exact_pair(P, x, 1, i, j);
@@ -553,13 +555,46 @@ int surf_run(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t
     }
   });
   // float32 sequential mean (SURF.py:162-163)
-  std::vector<double> avg(n);
+  S.avg.assign((size_t)n, 0.0);
   parallel_for(n, n_jobs, [&](int64_t i) {
     if (i < r_lo || i >= r_hi) return;  // not a focal sample of this call
     float s = 0.0f;
     for (int64_t j = 0; j < n; j++) s += Df[(size_t)i * n + j];
-    avg[i] = (double)s / (double)(n - 1);
+    S.avg[i] = (double)s / (double)(n - 1);
   });
+}
+
+// surf_run's fast-accumulation pair loop and weighted sum on that state, with
+// P's labels.
+int surf_fast_sums(const Prepared& P, const SurfShared& S, int n_jobs, int64_t r_lo, int64_t r_hi,
+                   double* scores) {
+  const int64_t n = P.n;
+  const std::vector<float>& Df = S.Df;
+  const std::vector<double>& avg = S.avg;
+  std::vector<PairW> pairs;
+  for (int64_t i = 0; i < n; i++)
+    for (int64_t j = i + 1; j < n; j++) {
+      const double df = (double)Df[(size_t)i * n + j];
+      const bool hit = P.labels[i] == P.labels[j];
+      // each side counts only for the focal samples [r_lo, r_hi)
+      const double wi = (i >= r_lo && i < r_hi) ? surf_weight(df < avg[i], hit, P.use_star) : 0.0;
+      const double wj = (j >= r_lo && j < r_hi) ? surf_weight(df < avg[j], hit, P.use_star) : 0.0;
+      const float w = (float)(wi + wj);
+      if (w != 0.0f) pairs.push_back({(int32_t)i, (int32_t)j, w});
+    }
+  std::vector<double> Sp(P.PW, 0.0);
+  weighted_sum(P, S.xs, pairs, n_jobs, Sp.data());
+  scatter_scores(P, Sp, scores);
+  return FS_OK;
+}
+
+int surf_run(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t r_hi,
+             double* scores) {
+  SurfShared sh;
+  surf_shared(P, x, n_jobs, r_lo, r_hi, sh);
+  const int64_t n = P.n;
+  const std::vector<float>& Df = sh.Df;
+  const std::vector<double>& avg = sh.avg;
   if (P.ref_accum) {
     // the reference's n_jobs = 1 order (fs_refacc.hip k_surf_chains): per
     // focal sample four float32 chains over ascending j of the float32-stored
@@ -594,21 +629,7 @@ int surf_run(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t
     ref_column_sums(temp, rows, nk, scores);
     return FS_OK;
   }
-  std::vector<PairW> pairs;
-  for (int64_t i = 0; i < n; i++)
-    for (int64_t j = i + 1; j < n; j++) {
-      const double df = (double)Df[(size_t)i * n + j];
-      const bool hit = P.labels[i] == P.labels[j];
-      // each side counts only for the focal samples [r_lo, r_hi)
-      const double wi = (i >= r_lo && i < r_hi) ? surf_weight(df < avg[i], hit, P.use_star) : 0.0;
-      const double wj = (j >= r_lo && j < r_hi) ? surf_weight(df < avg[j], hit, P.use_star) : 0.0;
-      const float w = (float)(wi + wj);
-      if (w != 0.0f) pairs.push_back({(int32_t)i, (int32_t)j, w});
-    }
-  std::vector<double> S(P.PW, 0.0);
-  weighted_sum(P, xs, pairs, n_jobs, S.data());
-  scatter_scores(P, S, scores);
-  return FS_OK;
+  return surf_fast_sums(P, sh, n_jobs, r_lo, r_hi, scores);
 }
 
 // The reference's float32 distance key of (i, j) (ReliefF.py:145-155):

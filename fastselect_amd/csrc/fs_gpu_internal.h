@@ -19,6 +19,7 @@
 //   fs_rrelieff.hip  RReliefF: the sums of a one-class ReliefF plan per target
 //   fs_labels.hip    MultiSURF permutation test: many labellings on one plan's decisions
 //   fs_relieff_labels.hip  ReliefF permutation test: many labellings on one pass 1
+//   fs_surf_labels.hip     SURF / SURF* permutation test: many labellings on one distance stage
 //
 // Kernel map and rooflines: DESIGN.md §3.  No float atomics touch scores:
 // every reduction has a fixed order, so two runs of the same input are
@@ -270,6 +271,14 @@ struct Plan {
   double rf_labels_ms[4] = {0, 0, 0, 0};
   hipEvent_t ev_rf_labels[2] = {nullptr, nullptr};
   hipEvent_t ev_rf_fast[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // plan_surf_score_labels (fs_surf_labels.hip): the last call's counts
+  // (plan_surf_labels_info; [0] < 0: no call yet), its summed stage times
+  // (plan_surf_labels_kernel_ms) and its events, taken on demand: [0..1] the
+  // distance and record stage, [2..3] the column sort, then per chunk of
+  // labellings the weights', the score kernel's and the star walk's
+  int64_t surf_labels_info[4] = {-1, 0, 0, 0};
+  double surf_labels_ms[4] = {0, 0, 0, 0};
+  std::vector<hipEvent_t> ev_surf_labels;
   // plan_score_targets (fs_rrelieff.hip): the selection's start / stop events
   // and per chunk of targets k_rrf_update's (plan_targets_kernel_ms), taken
   // on demand; rrf_chunks: chunks the last completed call walked (-1: none)
@@ -378,6 +387,9 @@ int row_guard(Plan* g);
 int apply_operand_width(Plan* g);
 int run_quantize_dist(Plan* g);
 int plan_score_surf(Plan* g, double* sums_dev);
+// SURF's distance stage alone: run_quantize_dist, then the means into thr and
+// (integer route) every stored distance as its float32 value
+int surf_distances(Plan* g);
 // fs_surfint.hip: after k_dist on a SURF plan's integer operands, the focal
 // rows' means into thr and every stored distance as its float32 value
 int surf_resolve(Plan* g);
@@ -393,6 +405,25 @@ bool star_split_fits(int64_t n, int32_t n_classes);
 int star_terms(Plan* g, hipStream_t st);
 int star_sums(Plan* g, hipStream_t st, bool continuous);
 int star_reduce(Plan* g, const double* counts, hipStream_t st);
+// fs_starterm.hip, for the SURF* permutation test (fs_surf_labels.hip).
+// star_lab_sort: every scored column of xsT [PW][n_pad] sorted once, without
+// the labels: sval[c][k] the k-th smallest value (a discrete column: its
+// float's bits, equal inside a run), sidx[c][k] its sample, tcol[c] = T_c =
+// the sum of d_c over all pairs, in float64 in the order of the sort.
+// star_lab_split: the items per segment and segments per column of the walk
+// (star_lab_seg hook honoured).  star_lab_walk: for the nb labellings of labT
+// ([n][32], codes in [0, 8)) the same-class sums Hs of every column into
+// hs[(c * nseg + seg) * 32 + b]; cnt: 4 * PW * nseg * 32 uint64 of scratch
+// (unused when nseg == 1), ncls: 64 uint64.  star_lab_apply: scores[b][o] =
+// 2 scores[b][o] - 2 (T_c - 2 Hs[c][b]) with the segments added in order.
+int star_lab_sort(Plan* g, const float* xsT, float* sval, uint16_t* sidx, double* tcol,
+                  hipStream_t st);
+void star_lab_split(const Plan* g, int64_t* seg_items, int64_t* nseg);
+int star_lab_walk(Plan* g, const float* sval, const uint16_t* sidx, const int32_t* labT, int nb,
+                  int64_t seg_items, int64_t nseg, uint64_t* ncls, uint64_t* cnt, double* hs,
+                  hipStream_t st);
+int star_lab_apply(Plan* g, const double* tcol, const double* hs, int64_t nseg, int nb,
+                   double* scores, hipStream_t st);
 // fs_pass2.hip
 int shard_segments(Plan* g);
 int choose_w8(int64_t units, double tiles_per_seg);  // fs_plan.hip
@@ -444,7 +475,13 @@ int relieff_prefix_ties(Plan* g, const std::vector<int32_t>& tie_rows, int64_t L
 // hook honoured); k_lab_score + k_lab_reduce of nb labellings into
 // scores[nb][n_kept] (part: nb * nseg * PW doubles; `scored`: an event
 // recorded between the two).  plan_score_labels launches through them too.
+// lab_records: the record stage of one call into g->mem_call (rec: nrec
+// records in whole groups per tile, goff; Nn[i] = |N_i|; wcnt: the weighted
+// pairs per wave quarter of a tile), with MultiSURF's decisions or (surf) SURF's:
+// (double)(float)D against thr.  One host synchronisation.
 int lab_transpose(Plan* g, const int32_t* lab_raw, int nb, int32_t* labT);
+int lab_records(Plan* g, bool surf, uint32_t** wcnt, int64_t** goff, uint32_t** Nn, int2** rec,
+                int64_t* nrec);
 void lab_score_split(const Plan* g, int64_t n_tiles, int64_t* seg_len, int64_t* nseg);
 int lab_score_reduce(Plan* g, const int2* rec, const int64_t* goff, const float* W,
                      int64_t n_tiles, int64_t seg_len, int64_t nseg, int nb, double* part,
@@ -456,6 +493,9 @@ int relieff_stir_sums(Plan* g, const int32_t* nbr, const int32_t* nfound, double
 int relieff_run_one(const Prepared& P, const void* x, int device, int64_t r_lo, int64_t r_hi,
                     double* sums_out, const double* seed = nullptr);
 // fs_plan.hip
+// whether one ReliefF / SURF plan holds the distance rows of every sample (a
+// one-shot call then scores without row panels)
+bool rows_fit_one_plan(const Prepared& P, int device);
 int plan_layout(Plan* g);
 int copy_sums(Plan* g, const double* sums_dev, double* sums_out);
 int surf_run_one(const Prepared& P, const void* x, int device, int64_t r_lo, int64_t r_hi,

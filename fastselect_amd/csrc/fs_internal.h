@@ -167,6 +167,7 @@ struct TestHooks {
   int64_t stir_seg_len = 0;    // >= 1: tiles per segment of k_stir_score (plan_stir; small n computes 1)
   int64_t labels_chunk = 0;    // 1..32: labellings per chunk of plan_score_labels (fs_labels.hip)
   int64_t labels_seg_len = 0;  // >= 1: tiles per workgroup of k_lab_score (plan_score_labels)
+  int64_t star_lab_seg = 0;    // >= 1: sorted items per segment of the SURF* label walk (fs_starterm.hip)
   int64_t rf_labels_route = 0; // 1: every labelling of plan_relieff_score_labels on the general route
   int64_t rf_labels_depth = 0; // 64 / 128 / 256: the candidate depth L of its fast route
   int64_t rf_labels_depth_cap = 0;  // >= 1: every row's usable prefix length cut to this (forces overflows)
@@ -450,6 +451,25 @@ int relieff_fast_sums(const Prepared& P, const void* x, const RelieffShared& S, 
 // scores[b * n_kept + k].
 int relieff_score_labels(const Prepared& P, const void* x, const int32_t* labels, int64_t B,
                          int n_jobs, double* scores);
+// What surf_run computes before it reads a label: the pass-2 operands, the
+// float32 distances and the means of the focal rows.
+struct SurfShared {
+  std::vector<float> xs;
+  std::vector<float> Df;
+  std::vector<double> avg;
+};
+void surf_shared(const Prepared& P, const void* x, int n_jobs, int64_t r_lo, int64_t r_hi,
+                 SurfShared& S);
+// surf_run's fast-accumulation pair loop and weighted sum on that state.
+int surf_fast_sums(const Prepared& P, const SurfShared& S, int n_jobs, int64_t r_lo, int64_t r_hi,
+                   double* scores);
+// SURF / SURF* permutation test (fs_surf_labels_cpu.cpp): the score sums of B
+// labellings of P's samples (fast accumulation, every focal row); row b has
+// the bits surf_run returns for a problem with labelling b as y.
+// scores[b * n_kept + k].
+// info (optional): out[4] of fs_plan_surf_labels_info.
+int surf_score_labels(const Prepared& P, const void* x, const int32_t* labels, int64_t B,
+                      int n_jobs, double* scores, int64_t* info = nullptr);
 int column_stats(const void* x, int x_is_f64, int64_t n, int64_t p, int64_t cap, int n_jobs,
                  void* colmin, void* colmax, int64_t* ndistinct);
 }  // namespace cpu
@@ -613,6 +633,23 @@ double plan_relieff_labels_kernel_ms(const Plan* g, int which);
 // scores_out[B * n_kept] divided by n.
 int relieff_labels_run(const Prepared& P, const void* x, int device, const int32_t* labels,
                        int64_t B, float* scores_out);
+// SURF / SURF* permutation test (fs_surf_labels.hip): the score sums of B
+// labellings (labels: host memory, [B][n]) of a SURF plan that owns every
+// focal row, into scores_dev[B * n_kept].  Distances, means and the record
+// list run once per call; per chunk of 32 labellings the weights, fs_labels.hip's
+// score kernel and, for SURF*, the walk over the sorted columns
+// (fs_starterm.hip).  plan_surf_labels_info: the weighted pairs listed, the
+// near sides, the chunks walked, 1 if the star walk ran.
+// plan_surf_labels_kernel_ms: distances + resolve + records (0), weights (1),
+// score kernel (2), column sort + star walk (3).
+int plan_surf_score_labels(Plan* g, const int32_t* labels, int64_t B, double* scores_dev);
+int plan_surf_labels_info(const Plan* g, int64_t* out4);
+double plan_surf_labels_kernel_ms(const Plan* g, int which);
+// One call from host arrays: plan (labelling 0 as y), then the labellings;
+// scores_out[B * n_kept] divided by n.  FS_ENOTSUP when the distance rows do
+// not fit one plan (surf_run would score in row panels).
+int surf_labels_run(const Prepared& P, const void* x, int device, const int32_t* labels,
+                    int64_t B, float* scores_out);
 int64_t ref_mask_words(const Plan* g);
 int plan_ref_masks(Plan* g, uint64_t* masks_dev);
 int plan_ref_pass2(Plan* g, const uint64_t* masks_dev, const double* counts_dev, int64_t row_lo,

@@ -57,7 +57,9 @@ typedef float lab_f16 __attribute__((ext_vector_type(16)));
 
 // near flags of pair (i0 + ii, j0 + jj) of owned tile t: bit 0 = j in N_i,
 // bit 1 = i in N_j; 0 for pairs outside the triangle.  The decisions of
-// pair_weight: d < thr on the stored distance.
+// pair_weight: d < thr on the stored distance; SURF: on its float32 value
+// (what the integer route stores already, and what the float64 route rounds to).
+template <bool SURF>
 __device__ __forceinline__ uint32_t lab_flags(const double* __restrict__ D, int64_t n,
                                               int64_t n_pad, int tiled, int2 win, int64_t t,
                                               int2 tl, int ii, int jj,
@@ -65,13 +67,15 @@ __device__ __forceinline__ uint32_t lab_flags(const double* __restrict__ D, int6
   const int64_t i0 = (int64_t)tl.x * kTile, j0 = (int64_t)tl.y * kTile;
   const int64_t i = i0 + ii, j = j0 + jj;
   if (!(i < n && j < n && (tl.x < tl.y || ii < jj))) return 0u;
-  const double d = D[d_rd(tiled, win, n_pad, t, i0, j0, ii, jj)];  // == D[i][j]
+  double d = D[d_rd(tiled, win, n_pad, t, i0, j0, ii, jj)];  // == D[i][j]
+  if (SURF) d = (double)(float)d;
   return (d < thr[i] ? 1u : 0u) | (d < thr[j] ? 2u : 0u);
 }
 
 // Weighted pairs per wave quarter of every tile: wave w of the workgroup
 // walks elements e = jj * 128 + ii in [w * 4096, (w + 1) * 4096), 64
 // consecutive ii at a time.  wcnt[t * 4 + w].
+template <bool SURF>
 __global__ __launch_bounds__(256) void k_lab_count(const double* __restrict__ D, int64_t n,
                                                    int64_t n_pad, int tiled, int2 win,
                                                    const int2* __restrict__ tiles,
@@ -83,7 +87,7 @@ __global__ __launch_bounds__(256) void k_lab_count(const double* __restrict__ D,
   uint32_t c = 0;
   for (int it = 0; it < 64; it++) {
     const int e = wave * 4096 + it * 64 + lane;
-    const uint32_t fl = lab_flags(D, n, n_pad, tiled, win, t, tl, e % kTile, e / kTile, thr);
+    const uint32_t fl = lab_flags<SURF>(D, n, n_pad, tiled, win, t, tl, e % kTile, e / kTile, thr);
     c += (uint32_t)__popcll(__ballot(fl != 0u));
   }
   if (lane == 0) wcnt[t * 4 + wave] = c;
@@ -126,6 +130,7 @@ __global__ __launch_bounds__(256) void k_lab_scan(const uint32_t* __restrict__ w
 // The records of every tile in element order (rec zeroed by the caller: the
 // padding of a tile's last group is (0, 0, no flags)), and Nn[i] += the near
 // sides of sample i.  rec[r] = (i, j | flags << 30).
+template <bool SURF>
 __global__ __launch_bounds__(256) void k_lab_fill(const double* __restrict__ D, int64_t n,
                                                   int64_t n_pad, int tiled, int2 win,
                                                   const int2* __restrict__ tiles,
@@ -143,7 +148,7 @@ __global__ __launch_bounds__(256) void k_lab_fill(const double* __restrict__ D, 
   for (int it = 0; it < 64; it++) {
     const int e = wave * 4096 + it * 64 + lane;
     const int ii = e % kTile, jj = e / kTile;
-    const uint32_t fl = lab_flags(D, n, n_pad, tiled, win, t, tl, ii, jj, thr);
+    const uint32_t fl = lab_flags<SURF>(D, n, n_pad, tiled, win, t, tl, ii, jj, thr);
     const uint64_t m = __ballot(fl != 0u);
     if (fl != 0u) {
       const int64_t r = pos + __popcll(m & ((1ull << lane) - 1ull));
@@ -425,6 +430,48 @@ int lab_score_reduce(Plan* g, const int2* rec, const int64_t* goff, const float*
   return launch_check("k_lab_reduce");
 }
 
+// The record stage of one call (buffers in g->mem_call): the weighted pairs
+// of every owned tile into rec (nrec records, whole groups per tile: goff),
+// Nn[i] = |N_i|, wcnt the counts per wave quarter.  surf: SURF's decisions.
+// One host synchronisation (the record count).
+int lab_records(Plan* g, bool surf, uint32_t** wcnt_out, int64_t** goff_out, uint32_t** Nn_out,
+                int2** rec_out, int64_t* nrec_out) {
+  const Prepared& Q = g->P;
+  const int64_t n = Q.n;
+  hipStream_t st = g->stream;
+  uint32_t *wcnt = nullptr, *Nn = nullptr;
+  int64_t* goff = nullptr;
+  FS_TRY(g->mem_call.alloc(&wcnt, (size_t)4 * g->n_tiles));
+  FS_TRY(g->mem_call.alloc(&goff, (size_t)g->n_tiles + 1));
+  FS_TRY(g->mem_call.alloc(&Nn, (size_t)n));
+  if (surf)
+    k_lab_count<true><<<(unsigned)g->n_tiles, 256, 0, st>>>(g->D, n, Q.n_pad, g->tiled, g->win,
+                                                            g->tiles, g->thr, wcnt);
+  else
+    k_lab_count<false><<<(unsigned)g->n_tiles, 256, 0, st>>>(g->D, n, Q.n_pad, g->tiled, g->win,
+                                                             g->tiles, g->thr, wcnt);
+  FS_TRY(launch_check("k_lab_count"));
+  k_lab_scan<<<1, 256, 0, st>>>(wcnt, g->n_tiles, goff);
+  FS_TRY(launch_check("k_lab_scan"));
+  int64_t ngroups = 0;
+  FS_HIP(hipMemcpyAsync(&ngroups, goff + g->n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  FS_HIP(hipStreamSynchronize(st));
+  const int64_t nrec = ngroups * kLabGroup;
+  int2* rec = nullptr;
+  FS_TRY(g->mem_call.alloc(&rec, (size_t)nrec));
+  FS_HIP(hipMemsetAsync(rec, 0, sizeof(int2) * (size_t)nrec, st));
+  FS_HIP(hipMemsetAsync(Nn, 0, sizeof(uint32_t) * (size_t)n, st));
+  if (surf)
+    k_lab_fill<true><<<(unsigned)g->n_tiles, 256, 0, st>>>(g->D, n, Q.n_pad, g->tiled, g->win,
+                                                           g->tiles, g->thr, wcnt, goff, rec, Nn);
+  else
+    k_lab_fill<false><<<(unsigned)g->n_tiles, 256, 0, st>>>(g->D, n, Q.n_pad, g->tiled, g->win,
+                                                            g->tiles, g->thr, wcnt, goff, rec, Nn);
+  FS_TRY(launch_check("k_lab_fill"));
+  *wcnt_out = wcnt, *goff_out = goff, *Nn_out = Nn, *rec_out = rec, *nrec_out = nrec;
+  return FS_OK;
+}
+
 static int labels_events(Plan* g, size_t count) {
   while (g->ev_labels.size() < count) {
     hipEvent_t e = event_get(g->device, true);
@@ -457,26 +504,10 @@ int plan_score_labels(Plan* g, const int32_t* labels, int64_t B, double* scores)
   // ---- records, once per call
   uint32_t *wcnt = nullptr, *Nn = nullptr, *H = nullptr;
   int64_t* goff = nullptr;
-  FS_TRY(g->mem_call.alloc(&wcnt, (size_t)4 * g->n_tiles));
-  FS_TRY(g->mem_call.alloc(&goff, (size_t)g->n_tiles + 1));
-  FS_TRY(g->mem_call.alloc(&Nn, (size_t)n));
-  FS_HIP(hipEventRecord(g->ev_labels[0], st));
-  k_lab_count<<<(unsigned)g->n_tiles, 256, 0, st>>>(g->D, n, Q.n_pad, g->tiled, g->win, g->tiles,
-                                                    g->thr, wcnt);
-  FS_TRY(launch_check("k_lab_count"));
-  k_lab_scan<<<1, 256, 0, st>>>(wcnt, g->n_tiles, goff);
-  FS_TRY(launch_check("k_lab_scan"));
-  int64_t ngroups = 0;
-  FS_HIP(hipMemcpyAsync(&ngroups, goff + g->n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  FS_HIP(hipStreamSynchronize(st));
-  const int64_t nrec = ngroups * kLabGroup;
   int2* rec = nullptr;
-  FS_TRY(g->mem_call.alloc(&rec, (size_t)nrec));
-  FS_HIP(hipMemsetAsync(rec, 0, sizeof(int2) * (size_t)nrec, st));
-  FS_HIP(hipMemsetAsync(Nn, 0, sizeof(uint32_t) * (size_t)n, st));
-  k_lab_fill<<<(unsigned)g->n_tiles, 256, 0, st>>>(g->D, n, Q.n_pad, g->tiled, g->win, g->tiles,
-                                                   g->thr, wcnt, goff, rec, Nn);
-  FS_TRY(launch_check("k_lab_fill"));
+  int64_t nrec = 0;
+  FS_HIP(hipEventRecord(g->ev_labels[0], st));
+  FS_TRY(lab_records(g, false, &wcnt, &goff, &Nn, &rec, &nrec));
   FS_HIP(hipEventRecord(g->ev_labels[1], st));
   // ---- the split of the score kernel: whole tiles per workgroup
   int64_t seg_len = 1, nseg = 1;

@@ -1248,8 +1248,9 @@ int plan_pass1(Plan* g, double* rowstats) {
   return FS_OK;
 }
 
-// SURF score sums of the plan's focal rows into sums_dev[n_kept].
-int plan_score_surf(Plan* g, double* sums_dev) {
+// SURF's distance stage: the distances of the plan's focal rows into D and
+// their means into thr (what plan_score_surf and plan_surf_score_labels share).
+int surf_distances(Plan* g) {
   const Prepared& Q = g->P;
   int rc = run_quantize_dist(g);  // integer or float64 distances
   if (rc == FS_OK && g->surf_int) {
@@ -1262,6 +1263,13 @@ int plan_score_surf(Plan* g, double* sums_dev) {
         g->D, Q.n, Q.n_pad, 1.0, g->r_lo, g->r_hi, g->thr);
     rc = launch_check("k_surf_avg");
   }
+  return rc;
+}
+
+// SURF score sums of the plan's focal rows into sums_dev[n_kept].
+int plan_score_surf(Plan* g, double* sums_dev) {
+  const Prepared& Q = g->P;
+  int rc = surf_distances(g);
   if (rc == FS_OK && Q.ref_accum) return surf_ref(g, sums_dev);  // fs_refacc.hip order
   if (rc == FS_OK) rc = run_weights(g, nullptr, ALGO_SURF, 1.0);
   if (rc == FS_OK) rc = run_pass2(g, sums_dev);

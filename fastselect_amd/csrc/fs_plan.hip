@@ -18,6 +18,7 @@ void plan_destroy(Plan* g) {
   for (auto& e : g->ev_rrf_sel) event_put(g->device, e, true);
   for (auto& e : g->ev_rrf) event_put(g->device, e, true);
   for (auto& e : g->ev_labels) event_put(g->device, e, true);
+  for (auto& e : g->ev_surf_labels) event_put(g->device, e, true);
   for (auto& e : g->ev_rf_labels) event_put(g->device, e, true);
   for (auto& e : g->ev_rf_fast) event_put(g->device, e, true);
   event_put(g->device, g->ev_fork, false);
@@ -932,6 +933,10 @@ static int64_t row_panel_rows(const Prepared& P, int device, int64_t rows) {
   if (avail <= per_row * kTile) return kTile;  // let the allocation report it
   const int64_t fit = (int64_t)(avail / per_row) / kTile * kTile;
   return std::max<int64_t>(kTile, std::min<int64_t>(fit, (rows + kTile - 1) / kTile * kTile));
+}
+
+bool rows_fit_one_plan(const Prepared& P, int device) {
+  return row_panel_rows(P, device, P.n) >= P.n;
 }
 
 // Score [r_lo, r_hi) in panels of `panel` rows (block-aligned), summing the

@@ -326,6 +326,241 @@ __global__ void k_star_alpha(int64_t n_pad, const double* __restrict__ counts, i
   alpha[i] = a;
 }
 
+// ---- the SURF* permutation test (fs_surf_labels.hip) ------------------------
+// Over B labellings the all-pairs part of SURF* is 2 (2 Hs[f, b] - T_f) with
+// T_f the sum of d_f over all pairs and Hs the same over the pairs of one
+// class under labelling b.  The sort does not read the labels: k_star_sort
+// sorts a column once per call (the sort, keys and run bounds of
+// k_star_terms), keeps the sorted values and samples and forms T_f; per chunk
+// of 32 labellings k_star_lab_walk walks the sorted column with the labels.
+// With r_c(k) the rank of item k inside its class and n_c the class size,
+//   continuous  Hs = sum_k v_k (2 r_c(k) - (n_c - 1))
+//   discrete    Hs = sum_k (r_c(k) - e_c(k)),  e_c(k) = the earlier items of
+//                                              k's class inside k's run.
+
+// Eight 16-bit counters (one per class; a count is at most n <= 24576) in two
+// 64-bit registers: a lane's per-class counts without indexed registers.
+__device__ __forceinline__ void pk_add(uint64_t& lo, uint64_t& hi, int c) {
+  const uint64_t inc = 1ull << ((c & 3) * 16);
+  if (c & 4) hi += inc;
+  else lo += inc;
+}
+__device__ __forceinline__ int pk_get(uint64_t lo, uint64_t hi, int c) {
+  return (int)((((c & 4) ? hi : lo) >> ((c & 3) * 16)) & 0xFFFFull);
+}
+
+// One column per workgroup: sval[c][k] = the k-th smallest value (DISC: the
+// bits of the stored float, equal inside a run of equal values), sidx[c][k]
+// its sample, tcol[c] = T_c: sum_k v_k (2 k - (n - 1)), or for a discrete
+// column sum_k (the items before k's run).  Fixed order; float64.
+template <int IPT, bool DISC>
+__global__ __launch_bounds__(kStThreads, FS_ST_MIN_WAVES) void k_star_sort(
+    const float* __restrict__ xsT, int64_t n, int64_t n_pad, int64_t c_first,
+    const int64_t* __restrict__ out_pos, float* __restrict__ sval, uint16_t* __restrict__ sidx,
+    double* __restrict__ tcol) {
+  using Sort = StSort<IPT>;
+  __shared__ StLds<IPT, DISC> sm;
+  const int64_t c = c_first + blockIdx.x;
+  const int tid = threadIdx.x;
+  if (out_pos[c] < 0) {
+    if (tid == 0) tcol[c] = 0.0;
+    return;
+  }
+  const int nn = (int)n;
+  const float* __restrict__ col = xsT + c * n_pad;
+  uint32_t key[IPT];
+  uint16_t idx[IPT];
+#pragma unroll
+  for (int j = 0; j < IPT; j++) {
+    const int i = j * kStThreads + tid;
+    key[j] = i < nn ? (DISC ? __float_as_uint(col[i]) : st_key(col[i])) : 0xFFFFFFFFu;
+    idx[j] = (uint16_t)i;
+  }
+  Sort().sort(key, idx, sm.u.sort);  // blocked: positions tid * IPT + j; padding last
+  __syncthreads();                   // the sort's storage is reused below
+  const int base = tid * IPT;
+  double acc = 0.0;
+  if (DISC) {
+#pragma unroll
+    for (int j = 0; j < IPT; j++)
+      if (base + j < nn) sm.u.d.key[base + j] = key[j];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < IPT; j++)
+      if (base + j < nn) acc += (double)st_bound<false>(sm.u.d.key, 0, base + j, key[j]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < IPT; j++)
+      if (base + j < nn) acc += (double)st_val(key[j]) * (double)(2 * (base + j) - (nn - 1));
+  }
+#pragma unroll
+  for (int j = 0; j < IPT; j++)
+    if (base + j < nn) {
+      sval[c * n_pad + base + j] = DISC ? __uint_as_float(key[j]) : st_val(key[j]);
+      sidx[c * n_pad + base + j] = idx[j];
+    }
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+  if (lane == 0) sm.ws[0][wave] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double t = 0.0;
+    for (int w = 0; w < kStWaves; w++) t += sm.ws[0][w];
+    tcol[c] = t;
+  }
+}
+
+// ncls[w * 32 + b]: the class sizes of labelling b of the chunk, packed
+// (w = 0: classes 0..3, 1: classes 4..7).  One workgroup.
+__global__ __launch_bounds__(256) void k_star_lab_ncls(const int32_t* __restrict__ labT, int64_t n,
+                                                       uint64_t* __restrict__ ncls) {
+  __shared__ uint64_t sh[2][256];
+  const int tid = threadIdx.x, m = tid & 31;
+  uint64_t lo = 0, hi = 0;
+  for (int64_t i = tid >> 5; i < n; i += 8) pk_add(lo, hi, labT[i * 32 + m]);
+  sh[0][tid] = lo;
+  sh[1][tid] = hi;
+  __syncthreads();
+  if (tid < 32) {
+    for (int k = 1; k < 8; k++) {
+      lo += sh[0][k * 32 + tid];
+      hi += sh[1][k * 32 + tid];
+    }
+    ncls[tid] = lo;
+    ncls[32 + tid] = hi;
+  }
+}
+
+constexpr int kSlB = 32;      // labellings per chunk: a lane owns one (labT's row)
+constexpr int kSlUnits = 8;   // (column, segment) units per 256-thread workgroup: one per half wave
+
+// A half wave walks segment seg (sorted items [seg * seg_items, ...)) of
+// column c: lane m owns labelling m of the chunk, the 32 lanes read one
+// 128-byte row labT[sidx[k]][0..31] per item, 32 items' rows requested before
+// the first is used.  The sorted values and samples are loaded one per lane and
+// handed round by ds_bpermute.
+// COUNT: the segment's class counts (cnt[.. + 0, 1]) and, for a discrete
+// column, those of its last run (cnt[.. + 2, 3]) -- launched only when a
+// column has more than one segment.  Else the walk: the class ranks start at
+// the sum of the earlier segments' counts (integers: exact in any order), a
+// discrete column's run counts at those of the run that reaches into the
+// segment, and the segment's part of Hs goes to hs[(c * nseg + seg) * 32 + m],
+// accumulated in float64 in the order of the sort.
+template <bool COUNT>
+__global__ __launch_bounds__(256) void k_star_lab_walk(
+    const float* __restrict__ sval, const uint16_t* __restrict__ sidx, int64_t n, int64_t n_pad,
+    int64_t PC, int64_t PW, const int64_t* __restrict__ out_pos, const int32_t* __restrict__ labT,
+    int64_t seg_items, int64_t nseg, const uint64_t* __restrict__ ncls, uint64_t* __restrict__ cnt,
+    double* __restrict__ hs) {
+  const int lane = threadIdx.x & 63, m = lane & 31;
+  const int64_t u = (int64_t)blockIdx.x * kSlUnits + (threadIdx.x >> 5);
+  const int64_t c = u / nseg, seg = u % nseg;
+  if (c >= PW || out_pos[c] < 0) return;  // a whole half wave
+  const bool disc = c >= PC;
+  const int64_t q0 = seg * seg_items, q1 = q0 + seg_items < n ? q0 + seg_items : n;
+  const float* __restrict__ sv = sval + c * n_pad;
+  const uint16_t* __restrict__ si = sidx + c * n_pad;
+  uint64_t* __restrict__ mycnt = cnt + ((c * nseg + seg) * 4) * kSlB + m;
+  uint64_t tl = 0, th = 0, rl = 0, rh = 0, nl = 0, nh = 0;
+  uint32_t prev = __float_as_uint(sv[q0]);
+  if (!COUNT) {
+    nl = ncls[m];
+    nh = ncls[32 + m];
+    for (int64_t t = 0; t < seg; t++) {
+      const uint64_t* __restrict__ p = cnt + ((c * nseg + t) * 4) * kSlB + m;
+      tl += p[0];
+      th += p[kSlB];
+    }
+    if (disc)
+      for (int64_t t = seg - 1; t >= 0; t--) {
+        // the run of the segment's first value reaches back into segment t
+        if (__float_as_uint(sv[(t + 1) * seg_items - 1]) != prev) break;
+        const uint64_t* __restrict__ p = cnt + ((c * nseg + t) * 4) * kSlB + m;
+        rl += p[2 * kSlB];
+        rh += p[3 * kSlB];
+        if (__float_as_uint(sv[t * seg_items]) != prev) break;  // and starts inside it
+      }
+  }
+  double acc = 0.0;
+  uint64_t iacc = 0;
+  for (int64_t qb = q0; qb < q1; qb += 32) {
+    const int64_t q = qb + m;
+    const float v = q < q1 ? sv[q] : 0.0f;
+    const int id = q < q1 ? (int)si[q] : 0;
+    int lab[32];
+#pragma unroll
+    for (int t = 0; t < 32; t++) lab[t] = labT[(int64_t)__shfl(id, t, 32) * kSlB + m];
+#pragma unroll
+    for (int t = 0; t < 32; t++) {
+      const float vt = __shfl(v, t, 32);
+      if (qb + t < q1) {
+        const int cls = lab[t];
+        if (disc) {
+          const uint32_t bits = __float_as_uint(vt);
+          if (bits != prev) {
+            rl = rh = 0;
+            prev = bits;
+          }
+          if (!COUNT) iacc += (uint64_t)(pk_get(tl, th, cls) - pk_get(rl, rh, cls));
+          pk_add(rl, rh, cls);
+        } else if (!COUNT) {
+          acc += (double)vt * (double)(2 * pk_get(tl, th, cls) - (pk_get(nl, nh, cls) - 1));
+        }
+        pk_add(tl, th, cls);
+      }
+    }
+  }
+  if (COUNT) {
+    mycnt[0] = tl;
+    mycnt[kSlB] = th;
+    mycnt[2 * kSlB] = rl;
+    mycnt[3 * kSlB] = rh;
+  } else {
+    hs[(c * nseg + seg) * kSlB + m] = disc ? (double)iacc : acc;
+  }
+}
+
+// scores[b][out_pos[c]] = 2 S_surf - 2 (T_c - 2 Hs[c][b]), the segments of Hs
+// added in segment order.
+__global__ __launch_bounds__(256) void k_star_lab_apply(const double* __restrict__ tcol,
+                                                        const double* __restrict__ hs,
+                                                        int64_t nseg, int64_t PW,
+                                                        const int64_t* __restrict__ out_pos,
+                                                        int64_t n_kept,
+                                                        double* __restrict__ scores) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t b = blockIdx.y;
+  if (c >= PW) return;
+  const int64_t o = out_pos[c];
+  if (o < 0) return;
+  double h = 0.0;
+  for (int64_t g = 0; g < nseg; g++) h += hs[(c * nseg + g) * kSlB + b];
+  const double s = scores[b * n_kept + o];
+  scores[b * n_kept + o] = 2.0 * s - 2.0 * (tcol[c] - 2.0 * h);
+}
+
+template <bool DISC>
+int launch_sort(Plan* g, const float* xsT, int64_t c_first, int64_t ncols, float* sval,
+                uint16_t* sidx, double* tcol, hipStream_t st) {
+  const Prepared& Q = g->P;
+  if (ncols <= 0) return FS_OK;
+  const unsigned grid = (unsigned)ncols;
+#define FS_ST(IPT)                                                                           \
+  k_star_sort<IPT, DISC><<<grid, kStThreads, 0, st>>>(xsT, Q.n, Q.n_pad, c_first, g->out_pos, \
+                                                      sval, sidx, tcol)
+  const int64_t ipt = (Q.n + kStThreads - 1) / kStThreads;
+  if (ipt <= 4) FS_ST(4);
+  else if (ipt <= 8) FS_ST(8);
+  else if (ipt <= 10) FS_ST(10);
+  else if (ipt <= 12) FS_ST(12);
+  else if (ipt <= 16) FS_ST(16);
+  else if (ipt <= 20) FS_ST(20);
+  else FS_ST(24);
+#undef FS_ST
+  return launch_check(DISC ? "k_star_sort<disc>" : "k_star_sort");
+}
+
 template <bool DISC, bool SUMS>
 int launch_terms(Plan* g, int64_t c_first, int64_t ncols, int64_t s_lo, int64_t s_hi,
                  double gamma, hipStream_t st) {
@@ -382,6 +617,55 @@ int run_alpha(Plan* g, const double* counts, hipStream_t st) {
 bool star_split_fits(int64_t n, int32_t n_classes) {
   return n >= 2 && n <= (int64_t)kStThreads * kStMaxIpt && n_classes >= 1 &&
          n_classes <= kStMaxClasses;
+}
+
+int star_lab_sort(Plan* g, const float* xsT, float* sval, uint16_t* sidx, double* tcol,
+                  hipStream_t st) {
+  const Prepared& Q = g->P;
+  if (Q.n < 2 || Q.n > (int64_t)kStThreads * kStMaxIpt) {
+    set_error("SURF* labellings: n outside the column sort's sizes (2 .. 24576)");
+    return FS_ENOTSUP;
+  }
+  FS_TRY((launch_sort<false>(g, xsT, 0, Q.PC, sval, sidx, tcol, st)));
+  return launch_sort<true>(g, xsT, Q.PC, Q.PW - Q.PC, sval, sidx, tcol, st);
+}
+
+// Segments so that columns x segments fill the device at small p (two units
+// per wave, 1024 SIMDs), none shorter than 256 items; whole columns otherwise.
+void star_lab_split(const Plan* g, int64_t* seg_items, int64_t* nseg) {
+  const Prepared& Q = g->P;
+  int64_t want = std::max<int64_t>(1, (4096 + Q.PW - 1) / Q.PW);
+  want = std::min<int64_t>(want, std::max<int64_t>(1, Q.n / 256));
+  int64_t items = ((Q.n + want - 1) / want + 31) / 32 * 32;
+  if (test_hooks().star_lab_seg >= 1) items = test_hooks().star_lab_seg;
+  *seg_items = items;
+  *nseg = (Q.n + items - 1) / items;
+}
+
+int star_lab_walk(Plan* g, const float* sval, const uint16_t* sidx, const int32_t* labT, int nb,
+                  int64_t seg_items, int64_t nseg, uint64_t* ncls, uint64_t* cnt, double* hs,
+                  hipStream_t st) {
+  const Prepared& Q = g->P;
+  (void)nb;  // the padding labellings of a chunk are walked too (labels 0) and never applied
+  k_star_lab_ncls<<<1, 256, 0, st>>>(labT, Q.n, ncls);
+  FS_TRY(launch_check("k_star_lab_ncls"));
+  const unsigned grid = (unsigned)((Q.PW * nseg + kSlUnits - 1) / kSlUnits);
+  if (nseg > 1) {
+    k_star_lab_walk<true><<<grid, 256, 0, st>>>(sval, sidx, Q.n, Q.n_pad, Q.PC, Q.PW, g->out_pos,
+                                                labT, seg_items, nseg, ncls, cnt, hs);
+    FS_TRY(launch_check("k_star_lab_walk<count>"));
+  }
+  k_star_lab_walk<false><<<grid, 256, 0, st>>>(sval, sidx, Q.n, Q.n_pad, Q.PC, Q.PW, g->out_pos,
+                                               labT, seg_items, nseg, ncls, cnt, hs);
+  return launch_check("k_star_lab_walk");
+}
+
+int star_lab_apply(Plan* g, const double* tcol, const double* hs, int64_t nseg, int nb,
+                   double* scores, hipStream_t st) {
+  const Prepared& Q = g->P;
+  k_star_lab_apply<<<dim3((unsigned)((Q.PW + 255) / 256), (unsigned)nb), 256, 0, st>>>(
+      tcol, hs, nseg, Q.PW, g->out_pos, Q.n_kept, scores);
+  return launch_check("k_star_lab_apply");
 }
 
 int star_terms(Plan* g, hipStream_t st) {

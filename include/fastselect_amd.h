@@ -551,6 +551,63 @@ FS_API int fs_relieff_score_labels(int backend, int device, const float* x, int6
                                    float* scores_out);
 FS_API int fs_plan_relieff_labels_info(const fs_plan* plan, int64_t out[4]);
 FS_API double fs_plan_relieff_labels_kernel_ms(const fs_plan* plan, int which);
+/* SURF / SURF* permutation test: many labellings on one distance pass
+ * (reference scoring: SURF.py:139-218).
+ *
+ * SURF's near sets N_i = { j != i : (double)(float)D_ij < avg_i } never read
+ * the labels: distances, their exact float32 resolution and the means run
+ * once for any number of labellings.  A near side weighs -1 for a hit and +1
+ * for a miss, so with s_b(i, j) = +1 where labelling b labels i and j
+ * differently, -1 where equally, and c_ij = near_i(j) + near_j(i),
+ *
+ *   S_surf[f, b] = sum over i < j of s_b(i, j) c_ij d_f(i, j)
+ *   S_star[f, b] = 2 S_surf[f, b] - 2 (T_f - 2 Hs[f, b])
+ *   T_f = sum over i < j of d_f(i, j),  Hs[f, b] = the same over the pairs of one class under b
+ *
+ * (fastselect_amd/csrc/fs_surf_labels.hip).  Hs comes from one label-free
+ * sort of the column per call and one walk over it per labelling.
+ *
+ * fs_plan_surf_score_labels (SURF.py:139-218): the score sums (not divided by
+ * n) of the plan's current feature set with labelling b as y; SURF or SURF*
+ * as the plan's use_star says.  labels[b * n + i]: host memory, int32,
+ * compared by equality only.  scores[b * n_kept + k] in the plan's memory
+ * space like fs_plan_score's sums (device memory for a GPU plan, host memory
+ * for a CPU plan).  The call is synchronous, runs the distance stage itself
+ * and honours fs_plan_set_features; a later fs_plan_score returns the bits it
+ * returned before.  B = 0: FS_OK, nothing written.  FS_EINVAL: not a SURF
+ * plan, or a NULL buffer.  FS_ENOTSUP: reference-order accumulation; a plan
+ * that does not own every focal row [0, n) or has world > 1; on the GPU for
+ * SURF*: n > 24576 or a label code outside [0, 8).  FS_EOOM: the weight buffer
+ * does not fit.  CPU backend: row b is bit for bit what fs_plan_score of a
+ * plan created with labelling b returns (any number of classes, any n).  GPU
+ * backend: float32 MFMA partials of at most 256 pairs folded into float64,
+ * the column terms in float64 in the order of the sort; no float atomics (the
+ * same call gives the same bits twice).
+ *
+ * fs_surf_score_labels (SURF.py:139-218): one call from host arrays (float64
+ * X, every column scored, labelling 0 as the plan's y); scores_out[b * p + f]
+ * divided by n.  B >= 1.  FS_ENOTSUP in reference order and, on the GPU, when
+ * the distance rows do not fit one plan (fs_surf_score would score in row
+ * panels).
+ *
+ * fs_plan_surf_labels_info (SURF.py:139-218): out[0..4) of the last completed
+ * call: the weighted pairs listed (pairs with a near side), the near sides
+ * sum_i |N_i|, the chunks of labellings walked (CPU: the labellings), 1 if
+ * the star walk ran.  FS_EINVAL before the first call.
+ *
+ * fs_plan_surf_labels_kernel_ms (SURF.py:139-218): summed HIP-event time in
+ * milliseconds of the last call (GPU only; -1 when unavailable).  which: 0 =
+ * distances + resolve + records (once per call), 1 = the weights kernels, 2 =
+ * the score kernel (both summed over the chunks), 3 = the column sort and the
+ * star walk (-1 when the star walk did not run). */
+FS_API int fs_plan_surf_score_labels(fs_plan* plan, const int32_t* labels, int64_t B,
+                                     double* scores);
+FS_API int fs_surf_score_labels(int backend, int device, const double* x, int64_t n, int64_t p,
+                                const int32_t* labels, int64_t B, const float* recip,
+                                const uint8_t* is_discrete, int use_star, int n_jobs,
+                                float* scores_out);
+FS_API int fs_plan_surf_labels_info(const fs_plan* plan, int64_t out[4]);
+FS_API double fs_plan_surf_labels_kernel_ms(const fs_plan* plan, int which);
 /* RReliefF: Relief for continuous targets (definitions: csrc/fs_rrelieff.h).
  * The neighbours of a focal sample are its k nearest other samples -- the
  * lists of a ReliefF plan with ONE class (fs_plan_create_relieff with
